@@ -62,6 +62,8 @@ WORKLOADS = {
     # the mesh of the design-loop parity test (tests/test_bench_line.py: --design-loop against the oracle's loop), the metric mesh's recipe
     "cant64": dict(el=(64, 32, 32), nlvls=4, nsmooth=2, ncoarse=20, cycles="1,3,1"),
 }
+# --dump-outputs: 5 arrays of at most 2^20 float64 entries (41.9 MB), within the 64 MB a dump may take
+DUMP_MAX_ENTRIES = 1 << 20
 
 
 def parse():
@@ -109,7 +111,27 @@ def parse():
                    help="parity object from the oracle's step alone (fx, gx, iteration count, every ||r_k||): no converged step, no 80-bit arbiter, "
                         "no dense-KE step -- for meshes where the arbiter's memory (20 B per non-zero of the assembled matrix) is too much")
     p.add_argument("--no-dense-check", action="store_true", help="parity object without the step on the dense-KE kernels (TP_NO_TILE / TP_NO_MACRO)")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="write what the last timed step computed as DIR/<name>.npy, float64: xTilde, xPhys, dfdx, dgdx, U and the "
+                        "scalars fx, gx, cg_its; an array of more than %d entries as the same seeded sample of %d of them in every run "
+                        "(at most 41 MB in all); rank 0's slab when --gpus > 1" % (DUMP_MAX_ENTRIES, DUMP_MAX_ENTRIES))
+    a = p.parse_args()
+    if a.dump_outputs and a.steps < 1:
+        p.error("--dump-outputs needs at least one timed step (--steps >= 1)")
+    return a
+
+
+def dump_outputs(out_dir, arrays, scalars):
+    """--dump-outputs: every array as float64 .npy, sampled at fixed positions (seed 0, sorted) beyond DUMP_MAX_ENTRIES entries"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        v = t.detach().reshape(-1).double().cpu().numpy()
+        if v.size > DUMP_MAX_ENTRIES:
+            v = v[np.sort(np.random.default_rng(0).choice(v.size, DUMP_MAX_ENTRIES, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+    for name, s in scalars.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.array([s], dtype=np.float64))
 
 
 def spawn_ranks(n, limit_s):
@@ -774,6 +796,10 @@ def main():
     dt = time.perf_counter() - t0
     wd.phase("after the timed region", 300)
     dt = max_over_ranks(dt)
+    if a.dump_outputs and rank == 0:
+        # before anything below reuses the case's vectors (MMA, stated cycle, parity steps)
+        dump_outputs(a.dump_outputs, {"xTilde": case.xt, "xPhys": case.xp, "dfdx": df, "dgdx": dg, "U": le.U},
+                     {"fx": info["fx"], "gx": info["gx"], "cg_its": info["its"]})
     t_step = dt / max(a.steps, 1)
     wd.partial.update({"value": ndof / t_step, "ms_per_step": 1e3 * t_step, "note": "partial line: only the timed region finished"})
     alg_bytes, flops, launches = le.pop_stats()

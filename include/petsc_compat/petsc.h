@@ -4,7 +4,7 @@
  *
  * Put  -I include/petsc_compat  where a PETSc build would put  -I $PETSC_DIR/include : ALL EIGHT sources of the
  * reference (main.cc, TopOpt.cc, MMA.cc, MPIIO.cc and the three hot-path classes) compile UNCHANGED against this
- * header and the small mpi.h beside it (host/build_ref_on_shim.sh and tests/test_reference_on_shim.py do
+ * header and the small mpi.h beside it (oracle/build_ref_on_shim.sh and tests/test_reference_on_shim.py do
  * exactly that, in the build container, storing nothing), and the resulting program runs the reference's
  * optimisation loop on the GPU.  Same names, argument order, ownership rules (XxxDestroy nulls the handle,
  * reference counted where the reference relies on it: PCMGSetInterpolation / KSPSetOperators retain) and error

@@ -244,3 +244,59 @@ def test_bench_workloads_are_consistent():
             if ez % world == 0 and (ez // world) % f == 0:                        # strong: bench.py refuses otherwise
                 assert ((ez // world) >> last_distributed) >= 2 or name in ("c1",), (name, "strong", world)
     assert b.WORKLOADS["c2"]["nlvls"] == 3 and b.WORKLOADS["c5"]["nlvls"] == 4      # stated by BASELINE.json configs[1], [4]
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    return b
+
+
+def test_dump_outputs_samples_large_arrays_at_fixed_positions(tmp_path):
+    """CPU: --dump-outputs writes float64 .npy files; an array larger than DUMP_MAX_ENTRIES keeps the same sorted, seeded
+    positions in every run, small arrays and scalars are written whole"""
+    import numpy as np
+    import torch
+    b = _bench_module()
+    n = b.DUMP_MAX_ENTRIES + 1000
+    big = torch.arange(n, dtype=torch.float64)
+    small = torch.linspace(0, 1, 77, dtype=torch.float32)
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), {"big": big, "small": small}, {"fx": 0.5, "cg_its": 7})
+    ba, bb = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert ba.dtype == np.float64 and ba.size == b.DUMP_MAX_ENTRIES and np.array_equal(ba, bb)
+    assert (np.diff(ba) > 0).all() and ba[0] >= 0 and ba[-1] < n          # distinct positions, in order
+    sm = np.load(tmp_path / "a" / "small.npy")
+    assert sm.dtype == np.float64 and np.array_equal(sm, small.double().numpy())
+    assert np.load(tmp_path / "a" / "fx.npy").tolist() == [0.5] and np.load(tmp_path / "a" / "cg_its.npy").tolist() == [7.0]
+    # the bound of one dump: five arrays of at most DUMP_MAX_ENTRIES float64 entries and three scalars
+    assert 5 * 8 * b.DUMP_MAX_ENTRIES + 3 * 8 <= 64 * 2 ** 20
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_is_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: the step's results after the timed region, whatever --steps is (every step starts from the same
+    design and a zero displacement), equal to the line's own figures"""
+    import numpy as np
+    runs = {}
+    for steps in (1, 3):
+        out = tmp_path / ("s%d" % steps)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tiny", "--steps", str(steps), "--warmup", "1",
+                            "--no-cube256", "--no-cpu-baseline", "--no-stated-cycle", "--design-loop", "0", "--dump-outputs", str(out)],
+                           capture_output=True, text=True, timeout=150, cwd=ROOT)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        d = json.loads([ln for ln in r.stdout.split("\n") if ln.strip()][-1])
+        assert d["steps"] == steps
+        z = {k: np.load(out / (k + ".npy")) for k in ("xTilde", "xPhys", "dfdx", "dgdx", "U", "fx", "gx", "cg_its")}
+        assert all(v.dtype == np.float64 for v in z.values())
+        ex, ey, ez = 32, 16, 16
+        assert z["xPhys"].size == z["dfdx"].size == ex * ey * ez and z["U"].size == 3 * (ex + 1) * (ey + 1) * (ez + 1)
+        assert z["cg_its"][0] == d["config"]["cg_its"] and np.isfinite(z["dfdx"]).all() and (z["dfdx"] <= 0).all()
+        runs[steps] = z
+    a, c = runs[1], runs[3]
+    assert np.array_equal(a["xTilde"], c["xTilde"]) and np.array_equal(a["xPhys"], c["xPhys"])
+    assert a["cg_its"][0] == c["cg_its"][0] and abs(a["fx"][0] / c["fx"][0] - 1) <= 1e-12
+    for k in ("dfdx", "dgdx", "U"):
+        assert np.abs(a[k] - c[k]).max() <= 1e-12 * np.abs(c[k]).max(), k

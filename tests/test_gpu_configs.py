@@ -3,8 +3,9 @@
 Every config is exercised twice: (1) AS CONFIGURED (load case + filter type + multigrid depth) on a small mesh
 against the CPU oracle, (2) at its FULL size through size-independent properties (symmetry / adjointness /
 constant preservation / true-residual / compliance identity) -- the oracle cannot finish those sizes in seconds.
-C3 and C5 are 8-GPU slab configurations: their slab geometry (8 ranks, 4 levels, 2 coarse layers per rank on the
-coarsest distributed level, replicated coarsest level) runs as 8 ranks sharing one GPU on a mesh reduced in x-y.
+C3 and C5 are 8-GPU slab configurations: their per-rank slab geometry (4 levels, 2 coarse layers per rank on the
+coarsest distributed level, replicated coarsest level) runs as 4 ranks sharing one GPU on a mesh reduced in x-y and z
+(tests/test_multirank.py).
 """
 import os
 

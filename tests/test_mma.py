@@ -190,11 +190,11 @@ def test_device_mma_several_constraints(orc, m):
         xd.copy_(dev(x))
 
 
-REF_MMA = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "host", "_refbuild", "ref_mma")
+REF_MMA = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "ref_mma")
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(not os.path.exists(REF_MMA), reason="host/_refbuild/ref_mma not built (build container only)")
+@pytest.mark.skipif(not os.path.exists(REF_MMA), reason="oracle/_ref/ref_mma not built (build container only)")
 @pytest.mark.parametrize("m,nproc", [(1, 1), (2, 1), (3, 2), (6, 1)])
 def test_device_mma_against_the_references_own_mma_class(tmp_path, m, nproc):
     """The REFERENCE's MMA.cc (compiled unchanged against the compat layer, host/ref_mma_driver.cc; on one or two slab

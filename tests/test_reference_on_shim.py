@@ -2,7 +2,7 @@
 
 CPU part (build container, where /root/reference exists): the reference's LinearElasticity.cc, Filter.cc and
 PDEFilter.cc compile UNCHANGED against the compat headers and link against libtopopt_petsc_shim.so
-(host/build_ref_on_shim.sh; nothing of the reference is stored in the repository, the binaries are git-ignored
+(oracle/build_ref_on_shim.sh; nothing of the reference is stored in the repository, the binaries are git-ignored
 build artefacts) -- and so do main.cc, TopOpt.cc, MMA.cc and MPIIO.cc: the reference's WHOLE program.  GPU part: that binary -- the reference's own classes on the MI355X path -- against the product's
 Python API on the same mesh; with no solver options at all the reference's hard-coded FGMRES/GMRES/SOR configuration
 runs as written (a one-device correctness mode), anything else is refused."""
@@ -14,18 +14,13 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "host", "_refbuild", "ref_on_shim")
+BIN = os.path.join(ROOT, "oracle", "_ref", "ref_on_shim")
 OPTS = ("-ksp_type cg -mg_levels_ksp_type chebyshev -mg_levels_pc_type jacobi "
         "-mg_coarse_ksp_type chebyshev -mg_coarse_pc_type jacobi").split()
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="reference sources only exist in the build container")
-def test_reference_sources_compile_and_link_against_the_shim():
-    r = subprocess.run(["bash", os.path.join(ROOT, "host", "build_ref_on_shim.sh")], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    assert os.path.exists(BIN) and os.path.exists(os.path.join(ROOT, "host", "_refbuild", "topopt_ref"))
-    # every PETSc symbol the three objects need is exported by the shim (the link above would have failed otherwise);
-    # and the shim's header declares nothing it does not define
+def _assert_shim_exports_its_header():
+    """the shim's header declares nothing the shim does not define"""
     src = open(os.path.join(ROOT, "include", "petsc_compat", "petsc.h")).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     names = set(re.findall(r"\b((?:Petsc|Vec|Mat|KSP|PC|DM|MPI_)[A-Za-z0-9_]*)\s*\(", src))
@@ -35,6 +30,21 @@ def test_reference_sources_compile_and_link_against_the_shim():
     exported = subprocess.run(["nm", "-D", "--defined-only", so], capture_output=True, text=True).stdout
     missing = [n for n in sorted(names) if not re.search(r"\b%s\b" % n, exported)]
     assert not missing, missing
+
+
+@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="reference sources only exist in the build container")
+def test_reference_sources_compile_and_link_against_the_shim():
+    r = subprocess.run(["bash", os.path.join(ROOT, "oracle", "build_ref_on_shim.sh")], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    assert os.path.exists(BIN) and os.path.exists(os.path.join(ROOT, "oracle", "_ref", "topopt_ref"))
+    # every PETSc symbol the three objects need is exported by the shim (the link above would have failed otherwise);
+    # and the shim's header declares nothing it does not define
+    _assert_shim_exports_its_header()
+
+
+def test_shim_exports_every_function_its_header_declares():
+    """the header half of the test above, which needs no reference sources"""
+    _assert_shim_exports_its_header()
 
 
 def _run(args, env=None):
@@ -49,7 +59,7 @@ def _numbers(out):
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(not os.path.exists(BIN), reason="host/_refbuild/ref_on_shim not built (build container only)")
+@pytest.mark.skipif(not os.path.exists(BIN), reason="oracle/_ref/ref_on_shim not built (build container only)")
 @pytest.mark.parametrize("ftype", [1, 2])
 def test_reference_classes_on_the_mi355x_path(ftype):
     import torch
@@ -80,7 +90,7 @@ def test_reference_classes_on_the_mi355x_path(ftype):
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(not os.path.exists(BIN), reason="host/_refbuild/ref_on_shim not built (build container only)")
+@pytest.mark.skipif(not os.path.exists(BIN), reason="oracle/_ref/ref_on_shim not built (build container only)")
 @pytest.mark.parametrize("ftype", [1, 2])
 def test_reference_hard_coded_solver_runs_as_written(ftype):
     """No solver options at all: the reference's SetUpSolver bodies configure FGMRES(100) + PCMG with GMRES(4)/SOR
@@ -119,7 +129,7 @@ def test_reference_hard_coded_solver_runs_as_written(ftype):
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(not os.path.exists(BIN), reason="host/_refbuild/ref_on_shim not built (build container only)")
+@pytest.mark.skipif(not os.path.exists(BIN), reason="oracle/_ref/ref_on_shim not built (build container only)")
 def test_unsupported_solver_configurations_are_refused_not_substituted():
     """anything but the two implemented configurations: PETSC_ERR_SUP = 56 with a message, never a silent substitute"""
     for extra, word in (["-ksp_type", "gmres"], "gmres"), (["-mg_levels_ksp_type", "richardson"], "richardson"), \
@@ -129,11 +139,11 @@ def test_unsupported_solver_configurations_are_refused_not_substituted():
         assert "REF_ON_SHIM failed: 56" in r.stdout
 
 
-TOPOPT_REF = os.path.join(ROOT, "host", "_refbuild", "topopt_ref")
+TOPOPT_REF = os.path.join(ROOT, "oracle", "_ref", "topopt_ref")
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(not os.path.exists(TOPOPT_REF), reason="host/_refbuild/topopt_ref not built (build container only)")
+@pytest.mark.skipif(not os.path.exists(TOPOPT_REF), reason="oracle/_ref/topopt_ref not built (build container only)")
 def test_whole_reference_program_unchanged_on_the_gpu_path(tmp_path):
     """ALL eight sources of the reference (main.cc, TopOpt.cc, MMA.cc, MPIIO.cc, LinearElasticity.cc, Filter.cc,
     PDEFilter.cc), compiled unchanged against include/petsc_compat and linked against the shim, run the
@@ -187,7 +197,7 @@ def _petsc_vecs(path):
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(not os.path.exists(TOPOPT_REF), reason="host/_refbuild/topopt_ref not built (build container only)")
+@pytest.mark.skipif(not os.path.exists(TOPOPT_REF), reason="oracle/_ref/topopt_ref not built (build container only)")
 def test_whole_reference_program_on_slab_ranks(tmp_path):
     """The reference's whole program, unchanged, as 2 and 4 processes (host/slabrun; the compat layer's MPI is the
     shared-memory job of host/slab_comm.h, its DMDA a 1 x 1 x R process grid of z-slabs with PETSc's ownership and
@@ -216,7 +226,7 @@ def test_whole_reference_program_on_slab_ranks(tmp_path):
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(not os.path.exists(BIN), reason="host/_refbuild/ref_on_shim not built (build container only)")
+@pytest.mark.skipif(not os.path.exists(BIN), reason="oracle/_ref/ref_on_shim not built (build container only)")
 @pytest.mark.parametrize("filt", [1, 2])
 def test_reference_classes_on_slab_ranks(filt):
     """The reference's LinearElasticity / Filter / PDEFilt classes on a synthetic design, 1 against 2 and 4 ranks:
@@ -235,7 +245,7 @@ def test_reference_classes_on_slab_ranks(filt):
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(not os.path.exists(TOPOPT_REF), reason="host/_refbuild/topopt_ref not built (build container only)")
+@pytest.mark.skipif(not os.path.exists(TOPOPT_REF), reason="oracle/_ref/topopt_ref not built (build container only)")
 @pytest.mark.parametrize("filt", [0, 2])
 def test_whole_reference_program_other_filters_on_two_ranks(tmp_path, filt):
     """-filter 0 (sensitivity filter) and -filter 2 (Helmholtz PDE filter: the reference's PDEFilt with its own KSP and
@@ -256,7 +266,7 @@ def test_whole_reference_program_other_filters_on_two_ranks(tmp_path, filt):
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(not os.path.exists(BIN), reason="host/_refbuild/ref_on_shim not built (build container only)")
+@pytest.mark.skipif(not os.path.exists(BIN), reason="oracle/_ref/ref_on_shim not built (build container only)")
 def test_capture_is_verified_against_what_the_reference_assembled():
     """TP_SHIM_VERIFY=1: MatSetValuesLocal normally keeps one number per element (the modulus) and one per filter (the
     radius).  In verify mode every 24x24 block of AssembleStiffnessMatrix is compared entry by entry (and index by
@@ -273,7 +283,7 @@ def test_capture_is_verified_against_what_the_reference_assembled():
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(not os.path.exists(TOPOPT_REF), reason="host/_refbuild/topopt_ref not built (build container only)")
+@pytest.mark.skipif(not os.path.exists(TOPOPT_REF), reason="oracle/_ref/topopt_ref not built (build container only)")
 @pytest.mark.parametrize("n", [1, 2])
 def test_restart_through_the_reference_code(tmp_path, n):
     """The reference's own restart path (TopOpt.cc:386-512: VecLoad of x, xPhys, xo1, xo2, U, L through the compat
@@ -307,7 +317,7 @@ def test_restart_through_the_reference_code(tmp_path, n):
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(not os.path.exists(TOPOPT_REF), reason="host/_refbuild/topopt_ref not built (build container only)")
+@pytest.mark.skipif(not os.path.exists(TOPOPT_REF), reason="oracle/_ref/topopt_ref not built (build container only)")
 def test_restart_files_cross_the_boundary_both_ways(tmp_path):
     """Restart files written by the REFERENCE's code (TopOpt::WriteRestartFiles + the compat binary viewer; the iteration
     file by the reference's own ofstream) are read by the product's Python driver, and the driver's files are read by
@@ -355,7 +365,7 @@ def test_restart_files_cross_the_boundary_both_ways(tmp_path):
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(not os.path.exists(TOPOPT_REF), reason="host/_refbuild/topopt_ref not built (build container only)")
+@pytest.mark.skipif(not os.path.exists(TOPOPT_REF), reason="oracle/_ref/topopt_ref not built (build container only)")
 def test_result_container_of_the_reference_writer_equals_the_products(tmp_path):
     """output_00000.dat written by the REFERENCE's MPIIO.cc (through the compat MPI-IO) against the one the product's
     Python writer (mpiio.MPIIO) produces for the same run: the same header, mesh (points, connectivity, offsets, types,
@@ -383,7 +393,7 @@ def test_result_container_of_the_reference_writer_equals_the_products(tmp_path):
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(not os.path.exists(BIN), reason="host/_refbuild/ref_on_shim not built (build container only)")
+@pytest.mark.skipif(not os.path.exists(BIN), reason="oracle/_ref/ref_on_shim not built (build container only)")
 @pytest.mark.parametrize("n,filt", [(1, 1), (2, 1), (1, 2), (2, 2)])
 def test_reference_loops_elementwise_against_the_device_kernels(tmp_path, n, filt):
     """What the REFERENCE's own host loops produce for a synthetic design -- the filtered density, the compliance
@@ -420,7 +430,7 @@ def test_reference_loops_elementwise_against_the_device_kernels(tmp_path, n, fil
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(not os.path.exists(TOPOPT_REF), reason="host/_refbuild/topopt_ref not built (build container only)")
+@pytest.mark.skipif(not os.path.exists(TOPOPT_REF), reason="oracle/_ref/topopt_ref not built (build container only)")
 def test_whole_reference_program_with_heaviside_projection(tmp_path):
     """-projectionFilter 1: the reference's Heaviside projection, its chain rule, the measure of non-discreteness and
     the beta continuation (Filter.cc:206-288) through the unchanged program against the product's driver with the
