@@ -23,12 +23,16 @@ import scipy.sparse as sp
 import scipy.sparse.linalg as spla
 
 
-def ssor_apply(A, r):
-    """one symmetric Gauss-Seidel sweep from a zero guess: forward (D + L) y = r, then backward (D + U) z = r - L y"""
+def ssor_parts(A):
+    """the triangular parts a symmetric sweep reads: (D + L, D + U, L), CSR"""
     A = A.tocsr()
-    DL = sp.tril(A, 0, format="csr")
-    DU = sp.triu(A, 0, format="csr")
-    L = sp.tril(A, -1, format="csr")
+    return sp.tril(A, 0, format="csr"), sp.triu(A, 0, format="csr"), sp.tril(A, -1, format="csr")
+
+
+def ssor_apply(A, r, parts=None):
+    """one symmetric Gauss-Seidel sweep from a zero guess: forward (D + L) y = r, then backward (D + U) z = r - L y;
+    parts: ssor_parts(A) built once (the same numbers, without rebuilding them on every call)"""
+    DL, DU, L = ssor_parts(A) if parts is None else parts
     y = spla.spsolve_triangular(DL, r, lower=True)
     return spla.spsolve_triangular(DU, r - L @ y, lower=False)
 
@@ -116,41 +120,59 @@ def gmres_left(A, pc, b, x0, m, maxit, rtol=0.0, atol=0.0, dtol=np.inf, test=Fal
     return x, its, np.array(hist)
 
 
+def fine_operator(orc, nx, ny, nz, KE, E=None, N=None):
+    """the fine-level matrix assembled from another element matrix (e.g. the library's KE_krylov() or KE_effective(),
+    rounded to double) with the same moduli and Dirichlet vector: an operator for RefSolver(A_outer=, A_level0=)"""
+    mg = orc.MG(nx, ny, nz, 3, 1)
+    mg.assemble(np.asarray(KE, dtype=np.float64), E, N)
+    return mg.csr(0)
+
+
 class RefSolver:
     """FGMRES around the PCMG V-cycle with GMRES level solvers; `mg` is an assembled oracle.MG (level matrices, Q1
-    transfer).  pc: 1 = PCSOR, 0 = PCJACOBI."""
+    transfer).  pc: 1 = PCSOR, 0 = PCJACOBI.
+
+    Optional operators, for comparisons with a library that applies other element matrices than the one `mg` was
+    assembled from (default: mg's fine-level matrix for both, i.e. one operator):
+      A_outer   the outer FGMRES's products: the initial and restart residual b - A x and A Z_j;
+      A_level0  the level-0 products inside the V-cycle: the smoother GMRES's A v and residuals, the residual before
+                the restriction.
+    PCSOR and PCJACOBI take their rows from mg's level matrices in every case, and so does the Galerkin hierarchy."""
 
     def __init__(self, mg, restart=100, rtol=1e-5, atol=1e-50, dtol=1e5, max_it=200, nsmooth=4, ncoarse=30, smooth_pc=1,
-                 coarse_pc=1, coarse_restart=30, coarse_rtol=1e-8):
+                 coarse_pc=1, coarse_restart=30, coarse_rtol=1e-8, A_outer=None, A_level0=None):
         self.mg, self.nlv = mg, mg.nlv
         self.A = [mg.csr(l) for l in range(mg.nlv)]
         self.dinv = [1.0 / A.diagonal() for A in self.A]
+        self.parts = [ssor_parts(A) for A in self.A]
+        self.A_outer = self.A[0] if A_outer is None else A_outer.tocsr()
+        self.A_ops = [self.A[0] if A_level0 is None else A_level0.tocsr()] + self.A[1:]
         self.o = dict(restart=restart, rtol=rtol, atol=atol, dtol=dtol, max_it=max_it, nsmooth=nsmooth, ncoarse=ncoarse,
                       smooth_pc=smooth_pc, coarse_pc=coarse_pc, coarse_restart=coarse_restart, coarse_rtol=coarse_rtol)
         self.coarse_its = 0
 
     def pc(self, l, kind):
-        return (lambda r: ssor_apply(self.A[l], r)) if kind == 1 else (lambda r: self.dinv[l] * r)
+        return (lambda r: ssor_apply(self.A[l], r, self.parts[l])) if kind == 1 else (lambda r: self.dinv[l] * r)
 
     def smooth(self, l, b, x0):
         o = self.o
-        return gmres_left(self.A[l], self.pc(l, o["smooth_pc"]), b, x0, o["nsmooth"], o["nsmooth"])[0]
+        return gmres_left(self.A_ops[l], self.pc(l, o["smooth_pc"]), b, x0, o["nsmooth"], o["nsmooth"])[0]
 
     def vcycle(self, l, b):
         o = self.o
         if l == self.nlv - 1:
-            x, its, _ = gmres_left(self.A[l], self.pc(l, o["coarse_pc"]), b, None, o["coarse_restart"], o["ncoarse"],
+            x, its, _ = gmres_left(self.A_ops[l], self.pc(l, o["coarse_pc"]), b, None, o["coarse_restart"], o["ncoarse"],
                                    o["coarse_rtol"], o["atol"], o["dtol"], test=True)
             self.coarse_its += its
             return x
         x = self.smooth(l, b, None)
-        rc = self.mg.restrict(l, b - self.A[l] @ x)
+        rc = self.mg.restrict(l, b - self.A_ops[l] @ x)
         x = x + self.mg.prolong(l, self.vcycle(l + 1, rc))
         return self.smooth(l, b, x)
 
     def solve(self, b, x0=None):
         """returns (x, its, recurrence residual norms ||b - A x_k||, k = 0..its)"""
-        o, A = self.o, self.A[0]
+        o, A = self.o, self.A_outer
         x = np.zeros_like(b) if x0 is None else x0.copy()
         m = max(1, o["restart"])
         bnorm = np.linalg.norm(b)

@@ -51,7 +51,7 @@ def test_bench_prints_one_json_line_with_the_contract_keys():
     assert em["library_export_equals_restatement"] is True and 0 < em["KE_eff_vs_KE"] <= 1e-15, em
     # round 6: the packed form keeps KE's translation residues (three values) -- its translation energy is KE's, to one rounding
     assert em["translation_residue_kept"] is True and 0 < em["translation_energy_KE"] and em["translation_energy_KE_eff_vs_KE"] <= 1e-3, em
-    # ... and the Krylov operator (A p, initial residual, MatMult) also KE's whole answer to a rigid translation
+    # ... and the Krylov operator (A p, initial residual, MatMultKrylov) also KE's whole answer to a rigid translation
     assert 0 < em["KE_krylov_vs_KE"] <= 1e-15 and em["translation_column_defect_KE_krylov"] <= 1e-18 < em["translation_column_defect_KE_eff"], em
     # (1) the GPU against the 80-bit arbiter on that operator: iteration counts, ||r_k||, compliance -- 1e-10, as north_star has it
     ar = p["arbiter"]

@@ -138,3 +138,47 @@ def test_outer_restarts(orc):
     assert its3 >= its100 > 3
     assert np.abs(x3 - U).max() <= 1e-8 * np.abs(U).max() and np.abs(x100 - U).max() <= 1e-8 * np.abs(U).max()
     assert np.linalg.norm(b - A @ x3) == pytest.approx(hist3[-1], rel=1e-5)
+
+
+class _UncachedSolver(refksp.RefSolver):
+    """RefSolver with the triangular parts of PCSOR rebuilt on every application (the sweep as it was first written)"""
+
+    def pc(self, l, kind):
+        return (lambda r: refksp.ssor_apply(self.A[l], r)) if kind == 1 else (lambda r: self.dinv[l] * r)
+
+
+def test_cached_triangular_parts_and_default_operators_change_no_bit(orc):
+    """RefSolver keeps each level's (D + L, D + U, L) once: a whole solve is bit for bit the solve with the parts rebuilt on
+    every sweep; and the optional operators, given the level-0 matrix itself, are the default"""
+    mg, b, _ = _mg(orc, 16, 8, 8, 3)
+    x, its, hist = refksp.RefSolver(mg, rtol=1e-8).solve(b)
+    xu, itsu, histu = _UncachedSolver(mg, rtol=1e-8).solve(b)
+    assert its == itsu > 3 and np.array_equal(x, xu) and np.array_equal(hist, histu)
+    A0 = mg.csr(0)
+    xo, itso, histo = refksp.RefSolver(mg, rtol=1e-8, A_outer=A0, A_level0=A0).solve(b)
+    assert itso == its and np.array_equal(xo, x) and np.array_equal(histo, hist)
+
+
+def test_translation_probe_separates_the_packed_form_from_the_krylov_operator(orc):
+    """The precondition of the ksp_mode 1 probes in tests/test_gpu_refksp.py, in 80-bit arithmetic (oracle/arbiter.py): on a
+    24 x 12 x 12 free mesh of unit moduli (h = 1/12), a rigid translation t = (1000, -2000, 500) at every node.  The
+    reference's KE answers it with ||KE t|| > 0 (its rows do not sum to exactly 0); the Krylov operator's element matrix
+    (KE_krylov) gives that norm to 2.7e-5, the packed form (KE_eff, what the V-cycle applies) 11.2 % short of it -- so a
+    residual formed with the packed form is visibly not the Krylov method's.  (On a 16 x 8 x 8 mesh the gap is 0.9 %: the
+    probe mesh matters.)"""
+    from oracle import arbiter as arb
+    from oracle.ke_effective import ke_effective, ke_krylov
+    ex, ey, ez = 24, 12, 12
+    nx, ny, nz, h = ex + 1, ey + 1, ez + 1, 1.0 / ey
+    KE = orc.hex8_ke_box(h, h, h, 0.3)
+    t = np.tile(np.array([1000.0, -2000.0, 500.0]), nx * ny * nz).astype(np.longdouble)
+
+    def norm(K):
+        y = arb.matfree_apply(nx, ny, nz, 3, np.asarray(K, dtype=np.longdouble), None, None, t)
+        return float(np.sqrt(np.sum(np.asarray(y, dtype=np.longdouble) ** 2)))
+
+    n_ke = norm(KE)
+    gap_eff, gap_kry = norm(ke_effective(KE)) / n_ke - 1, norm(ke_krylov(KE)) / n_ke - 1
+    assert 3.9e-12 < n_ke < 4.1e-12                      # 3.98668e-12
+    assert -0.115 < gap_eff < -0.110                     # -0.11243
+    assert abs(gap_kry) <= 5e-5                          # -2.66e-5

@@ -303,8 +303,10 @@ class LinearElasticity:
         return hi.astype(np.longdouble) + lo.astype(np.longdouble)
 
     def KE_krylov(self):
-        """the element matrix of the Krylov operator (the plain products: A p and the initial residual of CG, MatMult): the packed
-        form plus the translation mode's column and row of T KE T / 64 as KE has them; numpy.longdouble array of 576"""
+        """the element matrix of the Krylov operator (the Krylov method's own products: A p and the initial residual of CG; A Z_j
+        and the initial / restart residual of the outer FGMRES in ksp_mode 1; MatMultKrylov -- MatMult applies the packed form,
+        KE_effective()): the packed form plus the translation mode's column and row of T KE T / 64 as KE has them;
+        numpy.longdouble array of 576"""
         import numpy as np
         hi, lo = np.zeros(576), np.zeros(576)
         _chk(self.L.tp_elasticity_get_ke_krylov(self.handle, hi.ctypes.data, lo.ctypes.data), "tp_elasticity_get_ke_krylov")
@@ -348,7 +350,7 @@ class LinearElasticity:
         return y
 
     def MatMultKrylov(self, u, y=None):
-        """the product CG multiplies with inside KSPSolve (the operator from KE_krylov(): KE's action to rounding on
+        """the product the Krylov method multiplies with inside KSPSolve, CG's and ksp_mode 1's outer FGMRES's (the operator from KE_krylov(): KE's action to rounding on
         translation-dominated fields); MatMult applies the packed form (KE_effective())"""
         y = torch.zeros_like(u) if y is None else y
         _chk(self.L.tp_elasticity_apply_krylov(self.handle, _ptr(u), _ptr(y)), "tp_elasticity_apply_krylov")

@@ -70,7 +70,7 @@ static_assert(symke_idx(7, 2, 2) == SYMKE_N - 1, "packed size");
 
 constexpr int SYMKE_NTOT = SYMKE_N + 3;  // + 1 / KE[c][c]: the nodal diagonal is KE[c][c] * (sum of the 8 adjacent moduli)
 // Round 6, the KRYLOV operator's extra entries.  The operator of the Krylov method itself (EPI_APPLY_DOT: A p of CG, and the
-// initial residual A x0; tp_elasticity_apply_krylov) also applies what is left of T KE T / 64 in the translation mode's
+// initial residual A x0; A Z_j and the initial / restart residual of ksp_mode 1's FGMRES, refksp.h; tp_elasticity_apply_krylov) also applies what is left of T KE T / 64 in the translation mode's
 // COLUMN (how every mode of the element answers a rigid translation: D[(p,r),(0,s)], 69 entries beside the three of the packed
 // form) and ROW (how the translation mode answers every other mode: D[(0,r),(p,s)], p >= 1, 63 entries) -- one-sided, as KE has
 // them, not averaged: KE's asymmetry (1.4e-17) is 10 % of these residues.  Why: a late CG residual is ~1e-5 ||b|| while the

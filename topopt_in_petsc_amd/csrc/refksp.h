@@ -337,6 +337,22 @@ struct RefKsp {
         return gmres(l, b, L.x, false, o.nsmooth, o.nsmooth, 0.0, 0.0, 0.0, false, o.smooth_pc, nullptr);
     }
 
+    // ---- the outer method's own products: the Krylov operator where the fine level has one (as in MGSolver::solve), the
+    // level-0 operator otherwise.  The V-cycle's level-0 products (smoother, residual before restriction) stay on op<>():
+    // they belong to the preconditioner, exactly as on the CG path.
+    bool krylov_op() const { return SYMKE_KRYLOV && DOF == 3 && mg->lv[0].use_tile; }
+    int outer_apply(double *u, double *y) { return krylov_op() ? mg->apply_krylov(u, y) : mg->apply(0, u, y); }
+    // r = b - A x with the outer operator
+    int outer_resid(double *x, const double *b, double *r) {
+        if (!krylov_op()) return resid(0, x, b, r);
+        Level<DOF> &L = mg->lv[0];
+        TP_TRY(mg->apply_krylov(x, r));
+        TP_LAUNCH(k_axpby, dim3(grid_for(L.own_n())), dim3(BLK), 0, grid->stream, r + L.own_off(), 1.0, b + L.own_off(), -1.0,
+                  L.own_n());
+        count_launch(grid);
+        return TP_OK;
+    }
+
     // ---- KSPSolve: FGMRES(restart) around the V-cycle --------------------------------------------
     int solve(const double *b, double *x, int *its_out, double *rnorm_out, double *bnorm_out, double *hist, int hist_cap) {
         const tp_solver_opts &o = mg->opt;
@@ -356,7 +372,7 @@ struct RefKsp {
         bool done = false;
         TP_TRY(ensure(oV, 0, nd));
         while (!done) {
-            TP_TRY(resid(0, x, b, oV.vec(0)));
+            TP_TRY(outer_resid(x, b, oV.vec(0)));
             double beta;
             TP_TRY(norm(0, oV.vec(0), &beta));
             res = beta;
@@ -376,7 +392,7 @@ struct RefKsp {
                 TP_TRY(ensure(oZ, j, nd));
                 TP_TRY(vcycle(0, oV.vec(j)));
                 TP_HIP(hipMemcpyAsync(oZ.vec(j), L.x, sizeof(double) * (size_t)nd, hipMemcpyDeviceToDevice, grid->stream));
-                TP_TRY(mg->apply(0, oZ.vec(j), oV.vec(j + 1)));
+                TP_TRY(outer_apply(oZ.vec(j), oV.vec(j + 1)));
                 double hn;
                 TP_TRY(arnoldi(0, oV, j, h.data(), &hn));
                 res = H.column(j, h.data());

@@ -754,7 +754,8 @@ static int ke_applied(const tp_elasticity *e, bool krylov, double *hi, double *l
     return TP_OK;
 }
 extern "C" int tp_elasticity_get_ke_effective(const tp_elasticity *e, double *hi, double *lo) { return ke_applied(e, false, hi, lo); }
-// The element matrix of the KRYLOV operator (the plain products A p, A x0, MatMult): KE_eff plus the translation mode's column
+// The element matrix of the KRYLOV operator (the Krylov method's products: A p, A x0 of CG; A Z_j and the outer residual of
+// ksp_mode 1's FGMRES; tp_elasticity_apply_krylov -- tp_elasticity_apply is the packed form): KE_eff plus the translation mode's column
 // and row of T KE T / 64 as KE has them (matfree_tile.h: SYMKE_KRYLOV).  Same double-double convention.
 extern "C" int tp_elasticity_get_ke_krylov(const tp_elasticity *e, double *hi, double *lo) { return ke_applied(e, true, hi, lo); }
 extern "C" int tp_elasticity_set_bc(tp_elasticity *e, const double *N) {
