@@ -13,6 +13,7 @@
 typedef int PetscErrorCode;
 typedef double PetscScalar;
 typedef int PetscInt;
+typedef enum { PETSC_FALSE, PETSC_TRUE } PetscBool;
 #define CHKERRQ(ierr)                                                      \
     do {                                                                   \
         if (ierr) {                                                        \
@@ -160,6 +161,11 @@ class MMA {
     MMA(tp_grid *grid, PetscInt n_global, PetscInt m_, Vec x) : m(m_) {
         err = tp_mma_create(&h, grid, x->n, n_global, m_, x->d);
     }
+    // user-defined subproblem penalization (MMA.cc:195-242)
+    MMA(tp_grid *grid, PetscInt n_global, PetscInt m_, Vec x, PetscScalar *a, PetscScalar *c, PetscScalar *d) : m(m_) {
+        err = tp_mma_create(&h, grid, x->n, n_global, m_, x->d);
+        if (!err) err = tp_mma_set_subproblem(h, a, c, d);
+    }
     ~MMA() { tp_mma_destroy(h); }
     PetscErrorCode SetOuterMovelimit(PetscScalar Xmin, PetscScalar Xmax, PetscScalar movlim, Vec x, Vec xmin, Vec xmax) {
         return tp_mma_set_outer_movelimit(h, Xmin, Xmax, movlim, x->d, xmin->d, xmax->d);
@@ -168,6 +174,25 @@ class MMA {
         std::vector<const double *> p((size_t)m);
         for (int i = 0; i < m; i++) p[(size_t)i] = dgdx[i]->d;
         return tp_mma_update(h, xval->d, dfdx->d, gx, p.data(), xmin->d, xmax->d, &inner);
+    }
+    // MMA.cc:362-370
+    PetscErrorCode SetAsymptotes(PetscScalar init, PetscScalar decrease, PetscScalar increase) {
+        return tp_mma_set_asymptotes(h, init, decrease, increase);
+    }
+    // MMA.h:53
+    PetscErrorCode ConstraintModification(PetscBool conMod) { return tp_mma_constraint_modification(h, conMod ? 1 : 0); }
+    // MMA.cc:372-384: an invalid type is reported and leaves type 0; the call itself returns 0
+    PetscErrorCode SetRobustAsymptotesType(PetscInt val) {
+        if (tp_mma_set_robust_asymptotes_type(h, val) == TP_ERR_ARG)
+            printf("ERROR in MMA.cc/h: RobustAsymptotesType cannot be set to: %d \n", val);
+        return 0;
+    }
+    // MMA.cc:428-496
+    PetscErrorCode KKTresidual(Vec xval, Vec dfdx, PetscScalar *fx, Vec *dgdx, Vec xmin, Vec xmax, PetscScalar *norm2,
+                               PetscScalar *normInf) {
+        std::vector<const double *> p((size_t)m);
+        for (int i = 0; i < m; i++) p[(size_t)i] = dgdx[i]->d;
+        return tp_mma_kkt_residual(h, xval->d, dfdx->d, fx, p.data(), xmin->d, xmax->d, norm2, normInf);
     }
     PetscScalar DesignChange(Vec x, Vec xold) {
         double ch = 0.0;

@@ -347,6 +347,22 @@ int tp_mma_get_state(const tp_mma *mma, double *lam, double *z, int *k);
  * restart_set = the restart constructor (MMA.cc:22-106): continue at outer iteration k with these. */
 int tp_mma_restart_get(const tp_mma *mma, double *xo1, double *xo2, double *U, double *L);
 int tp_mma_restart_set(tp_mma *mma, int k, const double *xo1, const double *xo2, const double *U, const double *L);
+/* The settings below take effect at the next Update and survive tp_mma_restart_set.
+ * The a/c/d constructors (MMA.cc:195-242; restart :22-106): the subproblem's penalty numbers, host arrays of m
+ * (NULL = keep the current values: a = 0, c = 1000, d = 0 after tp_mma_create).  d is stored; MMA.cc never reads it. */
+int tp_mma_set_subproblem(tp_mma *mma, const double *a, const double *c, const double *d);
+/* SetAsymptotes (MMA.cc:362-370): asymptote initialisation, decrease and increase factors */
+int tp_mma_set_asymptotes(tp_mma *mma, double init, double decrease, double increase);
+/* SetRobustAsymptotesType (MMA.cc:372-384; GenSub :574-589): 0 (default) or 1 (wider L/U clamps, asymptotes of a
+ * variable outside [xmin, xmax] re-centred on it); any other value: type 0 and TP_ERR_ARG */
+int tp_mma_set_robust_asymptotes_type(tp_mma *mma, int val);
+/* ConstraintModification (MMA.h:53; GenSub :604-612): on != 0 adds p0/q0's convexifying terms to pij/qij */
+int tp_mma_constraint_modification(tp_mma *mma, int on);
+/* KKTresidual (MMA.cc:428-496) at the multipliers of the last Update (lam = y = z = 0 before the first one):
+ * argument convention of tp_mma_update (x, dfdx, xmin, xmax [dev]; gx host array of m constraint values; dgdx host
+ * array of m device pointers).  norm2 / normInf: over all ranks. */
+int tp_mma_kkt_residual(tp_mma *mma, const double *x, const double *dfdx, const double *gx, const double *const *dgdx,
+                        const double *xmin, const double *xmax, double *norm2, double *normInf);
 
 /* ---- streaming helpers used by the driver (main.cc:68-73, TopOpt.cc) ----- */
 int tp_vec_scale(tp_grid *g, double *x, double a, long n);

@@ -560,7 +560,9 @@ class Filter:
 class MMA:
     """MMA (MMA.h:29-140) on the device: the design vectors stay in HBM."""
 
-    def __init__(self, grid, x, m=1, n_global=None):
+    def __init__(self, grid, x, m=1, n_global=None, a=None, c=None, d=None):
+        """a, c, d: the subproblem's penalty numbers of the a/c/d constructors (MMA.cc:195-242), each a sequence of m
+        or one number for all j; None keeps the defaults a = 0, c = 1000, d = 0"""
         self.grid, self.L, self.m = grid, grid.L, m
         self.handle = C.c_void_p()
         n_loc = x.numel()
@@ -568,6 +570,17 @@ class MMA:
         _chk(self.L.tp_mma_create(C.byref(self.handle), grid.handle, n_loc, n_glob, m, _ptr(x)), "tp_mma_create")
         grid._adopt(self)
         self.last_inner = 0
+        if a is not None or c is not None or d is not None:
+            _chk(self.L.tp_mma_set_subproblem(self.handle, self._m_array(a), self._m_array(c), self._m_array(d)),
+                 "tp_mma_set_subproblem")
+
+    def _m_array(self, v):
+        if v is None:
+            return None
+        v = [float(v)] * self.m if isinstance(v, (int, float)) else [float(t) for t in v]
+        if len(v) != self.m:
+            raise ValueError("need %d values, got %d" % (self.m, len(v)))
+        return (C.c_double * self.m)(*v)
 
     def close(self):
         if getattr(self, "handle", None):
@@ -591,6 +604,27 @@ class MMA:
         _chk(self.L.tp_mma_update(self.handle, _ptr(x), _ptr(dfdx), g, dg, _ptr(xmin), _ptr(xmax), C.byref(it)),
              "tp_mma_update")
         self.last_inner = it.value
+
+    def SetAsymptotes(self, init, decrease, increase):
+        """MMA::SetAsymptotes (MMA.cc:362-370); from the next Update on"""
+        _chk(self.L.tp_mma_set_asymptotes(self.handle, float(init), float(decrease), float(increase)), "tp_mma_set_asymptotes")
+
+    def SetRobustAsymptotesType(self, val):
+        """MMA::SetRobustAsymptotesType (MMA.cc:372-384): 0 or 1; any other value leaves type 0 and raises"""
+        _chk(self.L.tp_mma_set_robust_asymptotes_type(self.handle, int(val)), "tp_mma_set_robust_asymptotes_type")
+
+    def ConstraintModification(self, conMod):
+        """MMA::ConstraintModification (MMA.h:53)"""
+        _chk(self.L.tp_mma_constraint_modification(self.handle, 1 if conMod else 0), "tp_mma_constraint_modification")
+
+    def KKTresidual(self, x, dfdx, gx, dgdx, xmin, xmax):
+        """MMA::KKTresidual (MMA.cc:428-496) at the multipliers of the last Update: returns (norm2, normInf)"""
+        g = (C.c_double * self.m)(*gx)
+        dg = (C.c_void_p * self.m)(*[_ptr(t) for t in dgdx])
+        n2, ni = C.c_double(), C.c_double()
+        _chk(self.L.tp_mma_kkt_residual(self.handle, _ptr(x), _ptr(dfdx), g, dg, _ptr(xmin), _ptr(xmax), C.byref(n2),
+                                        C.byref(ni)), "tp_mma_kkt_residual")
+        return n2.value, ni.value
 
     def DesignChange(self, x, xold):
         ch = C.c_double()

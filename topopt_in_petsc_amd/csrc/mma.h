@@ -14,6 +14,10 @@ struct MmaLam {
 };
 
 // GenSub: asymptotes, move limits, p/q coefficients; partials[j*nb + b] = sum pij/(U-x) + qij/(x-L)
+// ROBUST: SetRobustAsymptotesType(1) (MMA.cc:574-589): wider L/U clamps, and the asymptotes of a variable outside
+// [xmin, xmax] re-centred on it.  CONMOD: ConstraintModification(true) (:604-608): pij/qij get p0/q0's convexifying
+// terms.  <0, 0> is the reference's default and the only instantiation the driver uses unless asked.
+template <int ROBUST, int CONMOD>
 __global__ __launch_bounds__(BLK) void k_mma_gensub(long n, int m, int k, double asyminit, double asymdec,
                                                     double asyminc, const double *__restrict__ x,
                                                     const double *__restrict__ xo1, const double *__restrict__ xo2,
@@ -41,10 +45,26 @@ __global__ __launch_bounds__(BLK) void k_mma_gensub(long n, int m, int k, double
             Li = xv - gamma * (x1 - L[i]);
             Ui = xv + gamma * (U[i] - x1);
             const double xmi = fmax(1.0e-5, xma_ - xmi_);
-            Li = fmax(Li, xv - 10.0 * xmi);
-            Li = fmin(Li, xv - 0.01 * xmi);
-            Ui = fmax(Ui, xv + 0.01 * xmi);
-            Ui = fmin(Ui, xv + 10.0 * xmi);
+            if (!ROBUST) {
+                Li = fmax(Li, xv - 10.0 * xmi);
+                Li = fmin(Li, xv - 0.01 * xmi);
+                Ui = fmax(Ui, xv + 0.01 * xmi);
+                Ui = fmin(Ui, xv + 10.0 * xmi);
+            } else {
+                Li = fmax(Li, xv - 100.0 * xmi);
+                Li = fmin(Li, xv - 1.0e-4 * xmi);
+                Ui = fmax(Ui, xv + 1.0e-4 * xmi);
+                Ui = fmin(Ui, xv + 100.0 * xmi);
+                const double xlo = xmi_ - 1.0e-5, xhi = xma_ + 1.0e-5;  // :579-580 reassign xmi / xma
+                if (xv < xlo) {
+                    Li = xv - (xhi - xv) / 0.9;
+                    Ui = xv + (xhi - xv) / 0.9;
+                }
+                if (xv > xhi) {
+                    Li = xv - (xv - xlo) / 0.9;
+                    Ui = xv + (xv - xlo) / 0.9;
+                }
+            }
         }
         L[i] = Li;
         U[i] = Ui;
@@ -56,7 +76,14 @@ __global__ __launch_bounds__(BLK) void k_mma_gensub(long n, int m, int k, double
         q0[i] = (xl * xl) * (fmax(0.0, -1.0 * df) + 0.001 * fabs(df) + 0.5 * feps / (Ui - Li));
         for (int j = 0; j < m; j++) {
             const double g = dgdx[j][i];
-            const double pj = (ux * ux) * fmax(0.0, g), qj = (xl * xl) * fmax(0.0, -1.0 * g);
+            double pj, qj;
+            if (!CONMOD) {
+                pj = (ux * ux) * fmax(0.0, g);
+                qj = (xl * xl) * fmax(0.0, -1.0 * g);
+            } else {
+                pj = (ux * ux) * (fmax(0.0, g) + 0.001 * fabs(g) + 0.5 * feps / (Ui - Li));
+                qj = (xl * xl) * (fmax(0.0, -1.0 * g) + 0.001 * fabs(g) + 0.5 * feps / (Ui - Li));
+            }
             pij[(long)j * n + i] = pj;
             qij[(long)j * n + i] = qj;
             bs[j] += pj / ux + qj / xl;
@@ -159,13 +186,74 @@ __global__ __launch_bounds__(BLK) void k_max_final(const double *__restrict__ pa
     if (threadIdx.x == 0) out[0] = s_m[0];
 }
 
+// KKTresidual (MMA.cc:452-474): per element ri = dfdx + sum_j lam_j dgdx_j (left to right), the bound multipliers
+// with their 1e-5 tolerances, and the three squared terms.  partials[b] = the workgroup's sum (block_sum),
+// partials[nb + b] = its max; k_sum_max_final finishes both.
+__global__ __launch_bounds__(BLK) void k_mma_kkt(long n, int m, MmaLam lm, const double *__restrict__ x,
+                                                 const double *__restrict__ xmin, const double *__restrict__ xmax,
+                                                 const double *__restrict__ dfdx, const double *const *dgdx,
+                                                 double *__restrict__ partials) {
+#pragma clang fp contract(off)
+    __shared__ double s_m[BLK];
+    double s = 0.0, mx = 0.0;
+    for (long i = blockIdx.x * (long)BLK + threadIdx.x; i < n; i += (long)gridDim.x * BLK) {
+        const double xv = x[i], lo = xmin[i], hi = xmax[i];
+        double ri = dfdx[i];
+        for (int j = 0; j < m; j++) ri += lm.lam[j] * dgdx[j][i];
+        double mu_min = 0.0, mu_max = 0.0;
+        if (xv < lo + 1.0e-5 && ri > 0.0) mu_min = ri;
+        if (xv > hi - 1.0e-5 && ri < 0.0) mu_max = -ri;
+        ri += -mu_min + mu_max;
+        s += ri * ri;
+        mx = fmax(fabs(ri), mx);
+        double resi = mu_min * (xv - lo);
+        s += resi * resi;
+        mx = fmax(fabs(resi), mx);
+        resi = mu_max * (hi - xv);
+        s += resi * resi;
+        mx = fmax(fabs(resi), mx);
+    }
+    const double t = block_sum(s);
+    s_m[threadIdx.x] = mx;
+    __syncthreads();
+    for (int o = BLK / 2; o > 0; o >>= 1) {
+        if (threadIdx.x < o) s_m[threadIdx.x] = fmax(s_m[threadIdx.x], s_m[threadIdx.x + o]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        partials[blockIdx.x] = t;
+        partials[gridDim.x + blockIdx.x] = s_m[0];
+    }
+}
+// out[0] = sum_b partials[b] (k_reduce_multi's order), out[1] = max_b partials[nb + b]
+__global__ __launch_bounds__(BLK) void k_sum_max_final(const double *__restrict__ partials, int nb, double *__restrict__ out) {
+    __shared__ double s_m[BLK];
+    double s = 0.0, v = 0.0;
+    for (int b = threadIdx.x; b < nb; b += BLK) {
+        s += partials[b];
+        v = fmax(v, partials[nb + b]);
+    }
+    s = block_sum(s);
+    s_m[threadIdx.x] = v;
+    __syncthreads();
+    for (int o = BLK / 2; o > 0; o >>= 1) {
+        if (threadIdx.x < o) s_m[threadIdx.x] = fmax(s_m[threadIdx.x], s_m[threadIdx.x + o]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        out[0] = s;
+        out[1] = s_m[0];
+    }
+}
+
 struct tp_mma {
     tp_grid *grid;
     long n, nglob;
     int m, k;
     double asyminit, asymdec, asyminc;
-    double a[MMA_MAXM], c[MMA_MAXM], y[MMA_MAXM], lam[MMA_MAXM], mu[MMA_MAXM], b[MMA_MAXM];
+    double a[MMA_MAXM], c[MMA_MAXM], d[MMA_MAXM], y[MMA_MAXM], lam[MMA_MAXM], mu[MMA_MAXM], b[MMA_MAXM];
     double z;
+    int robust, conmod;  // SetRobustAsymptotesType (0 | 1), ConstraintModification
     double *L, *U, *alpha, *beta, *p0, *q0, *pij, *qij, *xo1, *xo2;
     const double **d_dgdx;  // [dev] m pointers
     double *red;            // [dev] m + m*m reduced values
@@ -203,9 +291,11 @@ extern "C" int tp_mma_create(tp_mma **out, tp_grid *g, long n_local, long n_glob
     M->asymdec = 0.7;
     M->asyminc = 1.2;
     M->z = 0.0;
+    M->robust = M->conmod = 0;
     for (int j = 0; j < m; j++) {
         M->a[j] = 0.0;  // MMA.cc:129-130
         M->c[j] = 1000.0;
+        M->d[j] = 0.0;
         M->y[j] = M->lam[j] = M->mu[j] = M->b[j] = 0.0;
     }
     const size_t nb = sizeof(double) * (size_t)n_local;
@@ -301,7 +391,9 @@ extern "C" int tp_mma_update(tp_mma *M, double *x, const double *dfdx, const dou
     TP_HIP(hipMemcpyAsync(M->d_dgdx, dgdx, sizeof(double *) * m, hipMemcpyHostToDevice, s));
     // ---- GenSub
     M->k++;
-    TP_LAUNCH(k_mma_gensub, dim3(nb), dim3(BLK), 0, s, n, m, M->k, M->asyminit, M->asymdec, M->asyminc, x, M->xo1,
+    auto gensub = M->robust ? (M->conmod ? k_mma_gensub<1, 1> : k_mma_gensub<1, 0>)
+                            : (M->conmod ? k_mma_gensub<0, 1> : k_mma_gensub<0, 0>);
+    TP_LAUNCH(gensub, dim3(nb), dim3(BLK), 0, s, n, m, M->k, M->asyminit, M->asymdec, M->asyminc, x, M->xo1,
                        M->xo2, xmin, xmax, dfdx, M->d_dgdx, M->L, M->U, M->alpha, M->beta, M->p0, M->q0, M->pij, M->qij,
                        M->part);
     count_launch(g, 8.0 * n * (12.0 + 3.0 * m), 40.0 * n);
@@ -420,5 +512,88 @@ extern "C" int tp_mma_restart_set(tp_mma *M, int k, const double *xo1, const dou
     TP_HIP(hipMemcpyAsync(M->U, U, nb, hipMemcpyDeviceToDevice, st));
     TP_HIP(hipMemcpyAsync(M->L, L, nb, hipMemcpyDeviceToDevice, st));
     M->k = k;
+    return TP_OK;
+}
+
+// The a/c/d constructors (MMA.cc:195-242, restart :22-106) = tp_mma_create (+ tp_mma_restart_set) + this.  d is kept
+// like the reference keeps it; its solver never reads it.
+extern "C" int tp_mma_set_subproblem(tp_mma *M, const double *a, const double *c, const double *d) {
+    if (!M) return TP_ERR_ARG;
+    for (int j = 0; j < M->m; j++) {
+        if (a) M->a[j] = a[j];
+        if (c) M->c[j] = c[j];
+        if (d) M->d[j] = d[j];
+    }
+    return TP_OK;
+}
+// SetAsymptotes (MMA.cc:362-370)
+extern "C" int tp_mma_set_asymptotes(tp_mma *M, double init, double decrease, double increase) {
+    if (!M) return TP_ERR_ARG;
+    M->asyminit = init;
+    M->asymdec = decrease;
+    M->asyminc = increase;
+    return TP_OK;
+}
+// SetRobustAsymptotesType (MMA.cc:372-384): anything but 0 or 1 falls back to 0
+extern "C" int tp_mma_set_robust_asymptotes_type(tp_mma *M, int val) {
+    if (!M) return TP_ERR_ARG;
+    M->robust = (val == 0 || val == 1) ? val : 0;
+    return (val == 0 || val == 1) ? TP_OK : TP_ERR_ARG;
+}
+// ConstraintModification (MMA.h:53)
+extern "C" int tp_mma_constraint_modification(tp_mma *M, int on) {
+    if (!M) return TP_ERR_ARG;
+    M->conmod = on ? 1 : 0;
+    return TP_OK;
+}
+// KKTresidual (MMA.cc:428-496): the element pass on the device (k_mma_kkt + k_sum_max_final), the sum over ranks
+// through the comm hook, the max over ranks through one slot per rank (as tp_mma_design_change), then the scalar
+// term of the constraints and the square root on the host in the reference's order (:487-493).
+extern "C" int tp_mma_kkt_residual(tp_mma *M, const double *x, const double *dfdx, const double *gx,
+                                   const double *const *dgdx, const double *xmin, const double *xmax, double *norm2,
+                                   double *normInf) {
+    if (!M || !x || !dfdx || !gx || !dgdx || !xmin || !xmax || !norm2 || !normInf) return TP_ERR_ARG;
+    tp_grid *g = M->grid;
+    hipStream_t s = g->stream;
+    const long n = M->n;
+    const int m = M->m;
+    const int nb = grid_for(n, 1024);
+    MmaLam lm;
+    for (int j = 0; j < m; j++) lm.lam[j] = M->lam[j];
+    TP_HIP(hipMemcpyAsync(M->d_dgdx, dgdx, sizeof(double *) * m, hipMemcpyHostToDevice, s));
+    TP_LAUNCH(k_mma_kkt, dim3(nb), dim3(BLK), 0, s, n, m, lm, x, xmin, xmax, dfdx, M->d_dgdx, M->part);
+    count_launch(g, 8.0 * n * (4.0 + m), (2.0 * m + 12.0) * n);
+    TP_LAUNCH(k_sum_max_final, dim3(1), dim3(BLK), 0, s, M->part, nb, M->red);
+    count_launch(g);
+    double n2, nI;
+    if (g->has_comm) {
+        TP_HIP(hipMemcpyAsync(g->comm.red, M->red, sizeof(double), hipMemcpyDeviceToDevice, s));
+        if (g->comm.allreduce_sum(g->comm.user, 1)) return TP_ERR_COMM;
+        TP_HIP(hipMemcpyAsync(M->red, g->comm.red, sizeof(double), hipMemcpyDeviceToDevice, s));
+    }
+    TP_HIP(hipMemcpyAsync(g->h_scal, M->red, sizeof(double) * 2, hipMemcpyDeviceToHost, s));
+    TP_HIP(hipStreamSynchronize(s));
+    n2 = g->h_scal[0];
+    nI = g->h_scal[1];
+    if (g->has_comm) {
+        const double mine = nI;
+        for (int o = 0; o < g->nranks; o += 16) {
+            const int cnt = g->nranks - o < 16 ? g->nranks - o : 16;
+            double slots[16] = {0};
+            if (g->rank >= o && g->rank < o + cnt) slots[g->rank - o] = mine;
+            TP_HIP(hipMemcpyAsync(g->comm.red, slots, sizeof(double) * cnt, hipMemcpyHostToDevice, s));
+            TP_HIP(hipStreamSynchronize(s));  // `slots` is a stack buffer
+            if (g->comm.allreduce_sum(g->comm.user, cnt)) return TP_ERR_COMM;
+            TP_HIP(hipMemcpyAsync(g->h_scal, g->comm.red, sizeof(double) * cnt, hipMemcpyDeviceToHost, s));
+            TP_HIP(hipStreamSynchronize(s));
+            for (int r = 0; r < cnt; r++) nI = fmax(nI, g->h_scal[r]);
+        }
+    }
+    double ri = 0.0;
+    for (int j = 0; j < m; j++) ri += M->lam[j] * (M->a[j] * M->z + M->y[j] - gx[j]);
+    n2 += pow(ri, 2.0);
+    nI = fmax(fabs(ri), nI);
+    *norm2 = sqrt(n2);
+    *normInf = nI;
     return TP_OK;
 }

@@ -51,6 +51,15 @@ class TopOpt:
     restartFileItr: str = None
     restartFileVecSol: str = None  # -restartFileVecSol: the state U (LinearElasticity.cc:590-606)
     onlyLoadDesign: bool = False
+    # MMA settings (MMA.h:29-69): None = the values of TopOpt.cc:391-397 (a = 0, c = 1000, d = 0), MMA.cc's asymptote
+    # factors 0.5 / 0.7 / 1.2, robust type 0, no constraint modification
+    aMMA: object = None
+    cMMA: object = None
+    dMMA: object = None
+    mma_asymptotes: tuple = None
+    mma_robust_asymptotes: int = 0
+    mma_constraint_modification: bool = False
+    kkt: bool = False              # MMA::KKTresidual after every Update -> kkt_norm2 / kkt_normInf in the record
     history: list = field(default_factory=list)
 
     def __post_init__(self):
@@ -68,7 +77,17 @@ class TopOpt:
         self.xTilde, self.xPhys = g.elem_vec(self.volfrac), g.elem_vec(self.volfrac)
         self.dfdx, self.dgdx = g.elem_vec(), [g.elem_vec() for _ in range(self.m)]
         self.xmin, self.xmax, self.xold = g.elem_vec(), g.elem_vec(), g.elem_vec(self.volfrac)
-        self.mma = MMA(g, self.x, self.m)
+        if self.aMMA is None and self.cMMA is None and self.dMMA is None:
+            self.mma = MMA(g, self.x, self.m)
+        else:
+            self.mma = MMA(g, self.x, self.m, a=0.0 if self.aMMA is None else self.aMMA,
+                           c=1000.0 if self.cMMA is None else self.cMMA, d=0.0 if self.dMMA is None else self.dMMA)
+        if self.mma_asymptotes is not None:
+            self.mma.SetAsymptotes(*self.mma_asymptotes)
+        if self.mma_robust_asymptotes:
+            self.mma.SetRobustAsymptotesType(self.mma_robust_asymptotes)
+        if self.mma_constraint_modification:
+            self.mma.ConstraintModification(True)
         self.fscale = 1.0
         self.itr = 0
         self._flip = True
@@ -97,6 +116,8 @@ class TopOpt:
         self.filt.Gradients(self.x, self.xTilde, self.dfdx, self.dgdx, self.projectionFilter, self.beta, self.eta)
         self.mma.SetOuterMovelimit(self.Xmin, self.Xmax, self.movlim, self.x, self.xmin, self.xmax)  # :81
         self.mma.Update(self.x, self.dfdx, [gx], self.dgdx, self.xmin, self.xmax)                # :85
+        if self.kkt:
+            kkt = self.mma.KKTresidual(self.x, self.dfdx, [gx], self.dgdx, self.xmin, self.xmax)
         ch = self.mma.DesignChange(self.x, self.xold)                                            # :89
         if self.projectionFilter:                                                                # :93-95
             self._increase_beta(gx, ch)
@@ -107,6 +128,8 @@ class TopOpt:
         rec = dict(itr=self.itr, fx=fx, fx_scaled=fxs, gx=gx, ch=ch, mnd=mnd, time=t2 - t1,
                    ksp_its=self.physics.last_its, ksp_rerr=self.physics.last_rnorm / self.physics.last_bnorm,
                    mma_inner=self.mma.last_inner)
+        if self.kkt:
+            rec["kkt_norm2"], rec["kkt_normInf"] = kkt
         self.history.append(rec)
         if verbose and self.rank == 0:
             print("It.: %i, True fx: %f, Scaled fx: %f, gx[0]: %f, ch.: %f, mnd.: %f, time: %f"

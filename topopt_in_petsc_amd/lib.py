@@ -146,6 +146,11 @@ SYMBOLS = {
     "tp_filter_mult_h": (_i, [_vp, _vp, _vp]),
     "tp_mma_restart_get": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "tp_mma_restart_set": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
+    "tp_mma_set_subproblem": (_i, [_vp, C.POINTER(_d), C.POINTER(_d), C.POINTER(_d)]),
+    "tp_mma_set_asymptotes": (_i, [_vp, _d, _d, _d]),
+    "tp_mma_set_robust_asymptotes_type": (_i, [_vp, _i]),
+    "tp_mma_constraint_modification": (_i, [_vp, _i]),
+    "tp_mma_kkt_residual": (_i, [_vp, _vp, _vp, C.POINTER(_d), C.POINTER(_vp), _vp, _vp, C.POINTER(_d), C.POINTER(_d)]),
     "tp_vec_scale": (_i, [_vp, _vp, _d, _l]),
     "tp_vec_set": (_i, [_vp, _vp, _d, _l]),
     "tp_synth_density": (_i, [_vp, _vp, C.c_uint64]),
