@@ -1,5 +1,5 @@
-"""The bench contract: `python bench.py` prints exactly ONE line on stdout, a JSON object with the driver's keys plus the
-`roofline` and `cpu_baseline` objects."""
+"""The bench contract: `python bench.py` prints exactly ONE line on stdout, a JSON object with the driver's keys; with
+`--full`, plus the `roofline` and `cpu_baseline` objects."""
 import json
 import os
 import subprocess
@@ -15,7 +15,7 @@ os.environ.setdefault("TP_BENCH_MEASURE_S", "0.05")   # the bench's micro-measur
 @pytest.mark.gpu
 def test_bench_prints_one_json_line_with_the_contract_keys():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tiny", "--steps", "2", "--warmup", "1", "--no-cube256",
-                        "--cpu-sample", "16x8x8"], capture_output=True, text=True, timeout=150, cwd=ROOT)
+                        "--cpu-sample", "16x8x8", "--full"], capture_output=True, text=True, timeout=150, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [ln for ln in r.stdout.split("\n") if ln.strip()]
     assert len(lines) == 1, r.stdout
@@ -68,11 +68,45 @@ def test_bench_prints_one_json_line_with_the_contract_keys():
 
 
 @pytest.mark.gpu
+def test_plain_bench_line_is_the_headline_alone():
+    """without --full a run sets up, warms up, times its steps and prints the line: the driver's keys and what the timed steps
+    counted themselves, nothing that takes steps, kernels or processes of its own -- and its step is the one a --full run times"""
+    lines = {}
+    for full in (False, True):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tiny", "--steps", "2", "--warmup", "1"] +
+                           (["--full", "--no-cpu-baseline"] if full else []), capture_output=True, text=True, timeout=150, cwd=ROOT)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        out = [ln for ln in r.stdout.split("\n") if ln.strip()]
+        assert len(out) == 1, r.stdout
+        lines[full] = json.loads(out[0])
+    d, f = lines[False], lines[True]
+    for k, t in (("metric", str), ("value", float), ("unit", str), ("n_gpus", int), ("steps", int), ("warmup", int),
+                 ("ms_per_step", float), ("higher_is_better", bool), ("scaling", str), ("dtype", str), ("data", str), ("config", dict)):
+        assert isinstance(d[k], t), (k, d.get(k))
+    assert d["metric"] == f["metric"] and d["unit"] == f["unit"] == "DOF-updates/s" and d["dtype"] == "f64" and d["higher_is_better"] is True
+    assert d["vs_baseline"] is None and d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and "error" not in d
+    assert d["value"] == pytest.approx(d["config"]["n_dof"] / (d["ms_per_step"] * 1e-3), rel=1e-6)
+    assert not {"roofline", "cpu_baseline", "parity", "other_scaling"} & set(d), sorted(d)
+    c, cf = d["config"], f["config"]
+    assert c["mma_ms_per_update"] is None and c["stated_cycle"] is None and c["design_loop"] is None
+    assert "roofline" in f and cf["mma_ms_per_update"] > 0
+    assert c["workload"] == cf["workload"] and c["kernel_launches_per_step"] == cf["kernel_launches_per_step"]
+    assert c["cg_its"] == cf["cg_its"] and c["fx"] == pytest.approx(cf["fx"], rel=1e-12)
+
+
+def test_plain_run_refuses_what_needs_full():
+    """CPU: the design loop is one of the extras of --full; asked for without it, the run stops before it starts"""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--design-loop", "3"], capture_output=True, text=True,
+                       timeout=60, cwd=ROOT)
+    assert r.returncode == 2 and "need --full" in r.stderr and not r.stdout.strip(), (r.returncode, r.stderr[-1000:])
+
+
+@pytest.mark.gpu
 def test_bench_exits_nonzero_when_a_parity_bound_breaks():
     """a bound of the parity object broken (here: made unreachable through TP_BENCH_TEST_PARITY_BOUND) -> the line is still
     printed, with "ok": false and the breach named, and the exit code is 4"""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tiny", "--steps", "1", "--warmup", "1", "--no-cube256",
-                        "--no-stated-cycle", "--cpu-sample", "16x8x8"], capture_output=True, text=True, timeout=150, cwd=ROOT,
+                        "--no-stated-cycle", "--cpu-sample", "16x8x8", "--full"], capture_output=True, text=True, timeout=150, cwd=ROOT,
                        env=dict(os.environ, TP_BENCH_TEST_PARITY_BOUND="1e-30"))
     assert r.returncode == 4, (r.returncode, r.stderr[-2000:])
     lines = [ln for ln in r.stdout.split("\n") if ln.strip()]
@@ -91,7 +125,7 @@ def test_design_loop_mode_against_the_oracle_loop():
     sys.path.insert(0, ROOT)
     from oracle import oracle as orc
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "cant64", "--steps", "1", "--warmup", "1", "--no-cube256",
-                        "--no-stated-cycle", "--no-cpu-baseline", "--design-loop", "5", "--design-loop-records"],
+                        "--no-stated-cycle", "--no-cpu-baseline", "--design-loop", "5", "--design-loop-records", "--full"],
                        capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.split("\n") if ln.strip()][0])
@@ -158,7 +192,7 @@ def _check_two_rank_line(r, scaling):
     assert one["its_equal"] and one["hist_max_rel_err"] <= 1e-10 and one["fx_rel_err"] <= 1e-10, one
 
 
-TWO_RANKS = ["--gpus", "2", "--same-device", "--backend", "gloo", "--workload", "tiny", "--steps", "2", "--warmup", "1"]
+TWO_RANKS = ["--gpus", "2", "--same-device", "--backend", "gloo", "--workload", "tiny", "--steps", "2", "--warmup", "1", "--full"]
 
 
 @pytest.mark.gpu
