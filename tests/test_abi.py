@@ -57,3 +57,42 @@ def test_product_never_imports_the_oracle():
                 txt = open(os.path.join(dp, f)).read()
                 assert "oracle" not in txt.replace("no CPU fallback", "").lower() or f == "__init__.py" and False, \
                     "%s mentions the oracle" % f
+
+
+CSRC = os.path.join(ROOT, "topopt_in_petsc_amd", "csrc")
+
+
+def test_only_switches_h_reads_the_environment():
+    """every environment variable of the product library has its accessor in csrc/switches.h; no other file there reads one"""
+    readers = sorted(f for f in os.listdir(CSRC) if "getenv" in open(os.path.join(CSRC, f)).read())
+    assert readers == ["switches.h"], readers
+
+
+# The library switches that bench.py, tests/*.py and tools/*.py put into the environment of a process that loads the
+# library, by the file that sets them.  An explicit list: TP_BENCH_*, TP_CHECK_OUT, TP_ERR_*, TP_LIB, TP_RANK, ... are not
+# library switches.  A name added to one of these files belongs here as well; a name may leave this list only with the
+# code that sets it.
+SWITCHES_SET_BY_NAME = {
+    "bench.py": ["TP_NO_TILE", "TP_NO_MACRO", "TP_FINE_V", "TP_NO_PDE_STENCIL"],
+    "tests/test_gpu_fine_generations.py": ["TP_FINE_V", "TP_FINE_SHAPE", "TP_TILE_KZ", "TP_NO_MACRO", "TP_DIA_NODE", "TP_DIA_SPLIT",
+                                           "TP_NO_DIA_SYM", "TP_LANCZOS_ON_MAIN", "TP_LANCZOS_TAILS", "TP_NO_REDUCE_TAIL"],
+    "tests/test_gpu_configs.py": ["TP_SMOOTH_GRAPH", "TP_COARSE_RUN", "TP_NO_COARSE_RUN", "TP_NO_COARSE_XCD", "TP_NO_LANCZOS_XCD",
+                                  "TP_DEBUG_SYNC"],
+    "tests/test_gpu_parity.py": ["TP_TEST_FORCE_GIVEUP", "TP_NO_COARSE_DIRECT", "TP_NO_COARSE_XCD", "TP_NO_LANCZOS_XCD",
+                                 "TP_CD_INVERT_COLUMNS", "TP_NO_FILTER_TILE", "TP_FILTER_ZMULTI", "TP_NO_REDUCE_TAIL"],
+    "tests/test_multirank.py": ["TP_REPLICATE_FROM", "TP_TEST_FORCE_GIVEUP"],
+    "tests/mp_gloo_worker.py": ["TP_OVERLAP", "TP_TEST_FORCE_GIVEUP"],
+    "tools/fine_ab.py": ["TP_FINE_V", "TP_TILE_KZ"],
+    "tools/r06_c3_hist_variants.py": ["TP_DIA_NODE", "TP_NO_DIA_SYM"],
+    "tools/r06_filter_ab.py": ["TP_FILTER_ZMULTI"],
+}
+
+
+def test_every_switch_set_by_name_exists():
+    """a switch that the benchmark, a test or a tool sets must exist in the library: dropped or renamed, it would be ignored silently"""
+    header = open(os.path.join(CSRC, "switches.h")).read()
+    for path, names in SWITCHES_SET_BY_NAME.items():
+        txt = open(os.path.join(ROOT, path)).read()
+        for name in names:
+            assert re.search(r"\b%s\b" % name, txt), "%s no longer names %s: update SWITCHES_SET_BY_NAME" % (path, name)
+            assert '"%s"' % name in header, "%s sets %s, which csrc/switches.h does not read" % (path, name)

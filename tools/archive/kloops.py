@@ -1,10 +1,10 @@
 #!/usr/bin/env python
-"""Loops of the hand-counted kernels (fine_dma.h) must contain no vector-memory wait or scratch access of the compiler's
+"""Loops of the hand-counted kernels (fine_u4.h) must contain no vector-memory wait or scratch access of the compiler's
 own: lists, per kernel of a hipcc -save-temps .s file, every inner loop with its compiler-inserted `s_waitcnt vmcnt`,
 scratch_ instructions and instruction count.   usage: kloops.py file.s [kernel-substring]"""
 import re, sys
 lines = open(sys.argv[1]).read().split("\n")
-pat = sys.argv[2] if len(sys.argv) > 2 else "k_fine_dma"
+pat = sys.argv[2] if len(sys.argv) > 2 else "k_fine_u4"
 i = 0
 while i < len(lines):
     l = lines[i]

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/topopt_amd.h"
+#include "switches.h"
 
 #define TP_HIP(x)                                              \
     do {                                                       \
@@ -25,40 +26,7 @@
 // Every kernel launch goes through TP_LAUNCH: a launch that the runtime rejects (LDS / register over-subscription
 // after a tuning change, bad grid) must not pass silently with stale output and a plausible timing.
 // TP_DEBUG_SYNC=1 additionally synchronises the device after every launch, so that an asynchronous fault is
-// reported at the launch that caused it (implies no graph capture).
-// The one-XCD persistent kernels (coarse_run.h: Chebyshev run, Lanczos run; coarse_direct.h: factorisation) rely on their
-// workgroups being co-resident.  When one of them gives up (its peers did not show up within ~1 s: a device shared with
-// another process' persistent kernels) the library redoes the work with the launch-per-step forms and keeps the
-// one-XCD forms OFF for the rest of the process (topopt_amd.hip: redo_without_xcd).
-inline bool &tp_xcd_disabled() {
-    static bool off = false;
-    return off;
-}
-// Round 6: the coarse factorisation, a chain of one-XCD kernels, runs on a side stream BESIDE the head of the
-// solve (mg.h: cd_pending) -- full-device kernels are queued while its later kernels start, so their co-residency is a
-// little less certain than on an idle device.  A give-up of THAT chain alone first costs the deferral (the factorisation is
-// joined at the end of the set-up again, round 4's behaviour), not the one-XCD forms; only a give-up without the deferral
-// switches them off.  Every recovery is counted (tp_xcd_status).
-inline bool &tp_defer_disabled() {
-    static bool off = false;
-    return off;
-}
-inline int &tp_giveup_count() {
-    static int n = 0;
-    return n;
-}
-// test switch TP_TEST_FORCE_GIVEUP = "<mode>" or "<mode>:<rank>": does it ask rank `rank` for recovery branch `mode`?
-// rank < 0: does it ask ANY rank (the collective agreement must then be reached by all of them)
-inline bool tp_test_force_giveup(int mode, int rank) {
-    const char *e = getenv("TP_TEST_FORCE_GIVEUP");
-    if (!e || atoi(e) != mode) return false;
-    const char *c = strchr(e, ':');
-    return rank < 0 || !c || atoi(c + 1) == rank;
-}
-inline bool tp_debug_sync() {
-    static const bool v = getenv("TP_DEBUG_SYNC") != nullptr && atoi(getenv("TP_DEBUG_SYNC")) != 0;
-    return v;
-}
+// reported at the launch that caused it (implies no graph capture; switches.h).
 inline int tp_launch_check(const char *what) {
     hipError_t e = hipGetLastError();
     if (e == hipSuccess && tp_debug_sync()) e = hipDeviceSynchronize();

@@ -367,7 +367,7 @@ static int filter_conv(tp_filter *f, double *out, const double *d1, const double
     TP_TRY(exchange_segments(g, f->xg + c * f->lay, f->xg, f->xg + (long)g->ez_own * f->lay,
                              f->xg + (long)(c + g->ez_own) * f->lay, c * f->lay, 1, c * f->lay));
     const dim3 tg((g->ex + 31) / 32, (g->ey + 3) / 4, (g->ez_own + 1) / 2);
-    static const bool no_tile = getenv("TP_NO_FILTER_TILE") != nullptr;
+    const bool no_tile = sw_no_filter_tile();
 #define TP_CONV_TILED(CC)                                                                                            \
     TP_LAUNCH(k_conv_filter_tiled<CC>, tg, dim3(256), 0, g->stream, g->ex, g->ey, g->ez_own, g->rank * g->ez_own, \
                        g->ez_glob, f->xg, f->wtab, out, d1, d2)
@@ -382,7 +382,7 @@ static int filter_conv(tp_filter *f, double *out, const double *d1, const double
     // outputs per thread along z at ElemConn 1, 2 (k_conv_filter_zmulti, bit-equal): by the number of workgroups the one-output
     // form would launch -- 128^3: 49.6 -> 36.1 us with four (two: 39.6), 128x64x64: 18.2 -> 15.6 with two (four: 16.4),
     // 48x24x24: 8.0 as it is (8.4 / 10.7); TP_FILTER_ZMULTI=0 / 2 / 4 forces one
-    static const int zm_env = getenv("TP_FILTER_ZMULTI") ? atoi(getenv("TP_FILTER_ZMULTI")) : -1;
+    const int zm_env = sw_filter_zmulti();
     const long wgs1 = (long)tg.x * tg.y * tg.z;
     const int zm = zm_env >= 0 ? zm_env : (wgs1 >= 8192 ? 4 : (wgs1 >= 1024 ? 2 : 0));
 #define TP_CONV_ZMULTI(CC, NO)                                                                                                     \

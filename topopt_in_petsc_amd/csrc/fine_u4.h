@@ -1,7 +1,7 @@
 // fine_u4.h -- the unmasked tiles of the fine-level operator, written for the INSTRUCTION COUNT of a step.
 //
-// What the probe runs of round 3 showed (tools/probe/fine_probe.hip): k_fine_tile and k_fine_dma spend the
-// same time per step although one waits for memory and the other does not -- 2.2-2.7 us per step with three waves per
+// What the probe runs of round 3 showed (profiles/r03_fine_probe*.txt): k_fine_tile and k_fine_dma (the
+// first LDS-DMA kernel, since removed) spend the same time per step although one waits for memory and the other does not -- 2.2-2.7 us per step with three waves per
 // SIMD, which is 3 waves x ~450 instructions x 4 cycles: a SIMD of this chip starts about ONE instruction per 4-cycle
 // turn, whatever its type.  The "memory-free" ablation of k_fine_dma (every descriptor empty) takes 234 us at 256^3,
 // the data-movement skeleton 245 us, the real kernel 295 us.  So the step is rewritten around its instruction count
@@ -12,14 +12,14 @@
 //   * descriptors advance by an addition per step; the "is this plane needed / inside the array" logic of k_fine_dma is
 //     one subtraction from a limit address and a max with 0;
 //   * the transformed top plane is carried to the next step (CARRY) where the registers allow it.
-// Queue discipline, hazards and waits: fine_dma.h (D = 2).
+// Queue discipline, hazards and waits: fine_lds_dma.h (D = 2).
 // Tiles that carry a Dirichlet condition (MASKED: one tile column in nine of a cantilever) take the mask bytes of their
 // four in-plane nodes straight into registers, one step ahead, with hand-counted loads like the epilogue operands:
-// + 4 loads and ~60 integer instructions per step.  (Staging them through LDS as fine_dma.h does costs 5 KB of LDS,
-// which is the third workgroup per CU; the compiler-counted loads of fine_dma.h drained the DMA queue every step:
+// + 4 loads and ~60 integer instructions per step.  (Staging them through LDS as k_fine_dma did costs 5 KB of LDS,
+// which is the third workgroup per CU; its compiler-counted loads drained the DMA queue every step:
 // 243 -> 307 us for the 256^3 product with only the x = 0 face clamped.)
 #pragma once
-#include "fine_dma.h"
+#include "fine_lds_dma.h"
 
 template <int TX, int TY>
 struct FineU4 {
@@ -94,7 +94,7 @@ __device__ __forceinline__ void fine_u4_run(const TileArgs &t, const NodeArgs &a
         Ru[0] = (int)(cu & 1), Ru[1] = Ru[0] ^ su_odd;
         Re[0] = (int)(ce & 1), Re[1] = Re[0] ^ se_odd;
     }
-    // ---- DMA units of this lane (fine_dma.h), wave-major: wave w issues instructions w * NIU_W .. of a plane
+    // ---- DMA units of this lane (fine_lds_dma.h), wave-major: wave w issues instructions w * NIU_W .. of a plane
     unsigned VU[2][NIU_W], VE[2][NIE_W];
     unsigned m0U[NIU_W], m0E[NIE_W];
 #pragma unroll

@@ -122,8 +122,7 @@ inline int finish_reduction(tp_grid *g, int slot) {
 // ever misbehave on another driver or firmware, TP_NO_REDUCE_TAIL=1 routes every such reduction through the former second
 // launch (k_reduce_final: same summation order, same bits): the kernels get no ticket and leave their partial sums only.
 inline unsigned *tail_ticket(tp_grid *g) {
-    static const bool off = getenv("TP_NO_REDUCE_TAIL") != nullptr;
-    return off ? nullptr : g->ticket;
+    return sw_no_reduce_tail() ? nullptr : g->ticket;
 }
 template <int NV>
 inline int finish_reduction(tp_grid *g, int slot);

@@ -23,7 +23,7 @@ extern "C" int tp_grid_create(tp_grid **out, const tp_grid_opts *o) {
     if (g->has_comm) {
         g->comm = g->comm_host = *o->comm;
         // second stream for the overlapped halos (TP_OVERLAP=0: every halo on the grid's stream, before its consumer)
-        const bool want = !(getenv("TP_OVERLAP") && atoi(getenv("TP_OVERLAP")) == 0);
+        const bool want = sw_overlap();
         if (want && hipStreamCreateWithFlags(&g->comm_stream, hipStreamNonBlocking) == hipSuccess &&
             hipEventCreateWithFlags(&g->ev_ready, hipEventDisableTiming) == hipSuccess)
             g->overlap = true;
@@ -647,13 +647,13 @@ extern "C" int tp_elasticity_create_ke(tp_elasticity **out, tp_grid *g, const tp
             // tuned kernel needs the reflection symmetry of a box element (always true here)
             SymKE sk;
             const double asym = make_sym_ke(e->KE, &sk);
-            L.sym_slot = (asym < 1e-12 && !getenv("TP_NO_TILE")) ? sym_slot_acquire(sk) : -1;
+            L.sym_slot = (asym < 1e-12 && !sw_no_tile()) ? sym_slot_acquire(sk) : -1;
             TP_HIP(hipMalloc((void **)&e->d_colmask, (size_t)q.plane()));
             TP_HIP(hipMemset(e->d_colmask, 0, (size_t)q.plane()));
             L.colmask = e->d_colmask;
             L.use_tile = L.sym_slot >= 0;
         }
-        if (l == 1 && e->mg.lv[0].use_tile && !getenv("TP_NO_MACRO") && o->ksp_mode == 0) {  // Gauss-Seidel needs rows
+        if (l == 1 && e->mg.lv[0].use_tile && !sw_no_macro() && o->ksp_mode == 0) {  // Gauss-Seidel needs rows
             // level 1 is applied from the fine densities (k_matfree_tile<.,1>): no stencil storage
             L.kind = LV_MACRO;
             L.use_tile = true;
@@ -1041,8 +1041,8 @@ static int elasticity_setup_from_E(tp_elasticity *e) {
     // while the factorisation is already under way on its own stream.  Same kernels, same data, same results.
     // Level 2's element matrices come straight from the fine moduli (k_galerkin_l2_fast, ~0.3 ms at 128^3) and do not
     // depend on level 1's kernels: side by side on a second stream, joined where level 2 continues.
-    static const bool no_l2_aside = getenv("TP_NO_L2_ASIDE") != nullptr || getenv("TP_NO_L2_FAST") != nullptr || tp_debug_sync();
-    static const bool two_pass = getenv("TP_NO_SETUP_REORDER") == nullptr;
+    const bool no_l2_aside = sw_no_l2_aside();
+    const bool two_pass = !sw_no_setup_reorder();
     bool l2_aside = false;
     if (macro1 && mg.nlv > 2 && !no_l2_aside) {
         if (!e->aux_stream) TP_HIP(hipStreamCreateWithFlags(&e->aux_stream, hipStreamNonBlocking));
@@ -1050,7 +1050,7 @@ static int elasticity_setup_from_E(tp_elasticity *e) {
         if (!e->aux_done) TP_HIP(hipEventCreateWithFlags(&e->aux_done, hipEventDisableTiming));
         Level<3> &C2 = mg.lv[2];
         const long nEc2 = C2.g.own_elems();
-        static const long nb2_env = getenv("TP_L2_BLOCKS") ? atol(getenv("TP_L2_BLOCKS")) : 512;
+        const long nb2_env = sw_l2_blocks();
         const unsigned nb2 = (unsigned)(nEc2 < nb2_env ? nEc2 : nb2_env);
         TP_HIP(hipEventRecord(e->aux_fork, s));
         TP_HIP(hipStreamWaitEvent(e->aux_stream, e->aux_fork, 0));
@@ -1088,9 +1088,9 @@ static int elasticity_setup_from_E(tp_elasticity *e) {
         } else if (l == 2 && macro1) {
             // all 64 fine moduli below an element at once (constants in registers); elements with a flagged
             // level-1 child go through the generic contraction with the compact rows
-            static const bool no_fast2 = getenv("TP_NO_L2_FAST") != nullptr;
+            const bool no_fast2 = sw_no_l2_fast();
             if (!no_fast2) {
-                static const long nb2_env = getenv("TP_L2_BLOCKS") ? atol(getenv("TP_L2_BLOCKS")) : 512;
+                const long nb2_env = sw_l2_blocks();
                 const unsigned nb2 = (unsigned)(nEc < nb2_env ? nEc : nb2_env);
                 if (l2_aside) {
                     TP_HIP(hipStreamWaitEvent(s, e->aux_done, 0));
