@@ -298,6 +298,12 @@ int tp_elasticity_restrict(tp_elasticity *e, int level, const double *rf, double
 int tp_elasticity_prolong_add(tp_elasticity *e, int level, const double *xc, double *xf);
 /* bytes moved / flops of the last call, by the algorithmic model of DESIGN.md */
 int tp_elasticity_last_stats(const tp_elasticity *e, double *alg_bytes, double *flops, long *kernel_launches);
+/* which kernel form the last operator application (apply, level_apply, smooth, ...) launched, for tests that force a form
+ * through the environment and must not pass on another one: form4[0] 1 fine tile kernel, 2 level 1 applied from the fine
+ * densities, 3 per-node matrix-free kernel, 4 stored stencil; [1] fine: generation 1..3, level 1: 1 if the Dirichlet
+ * correction was fused, stencil: threads per row 9 / 3 / 1; [2] fine: tile 0 = 15 x 15 nodes, 1 = 16x16, 2 = 32x8,
+ * 3 = 32x16, stencil: 1 = node form; [3] fine and level 1: z-chunk length, stencil: 1 = mirrored reads */
+int tp_elasticity_last_op_form(const tp_elasticity *e, int *form4);
 
 /* ---- density / sensitivity filter (Filter.cc) --------------------------- */
 typedef struct tp_filter tp_filter;
@@ -308,6 +314,9 @@ int tp_filter_create(tp_filter **f, tp_grid *g, int filterType, double rmin, con
 int tp_filter_mult_h(tp_filter *f, const double *x, double *y);
 int tp_filter_destroy(tp_filter *f);
 int tp_filter_stencil_width(const tp_filter *f);        /* ElemConn, Filter.cc:326 */
+/* which cone-filter kernel the last convolution (project, gradients, mult_h) launched, for tests: 1 LDS-tiled, 2 several
+ * outputs per thread along z, 3 wide (ElemConn 3..8), 4 streamed ring (9..24), 5 generic loop; 0 none yet */
+int tp_filter_last_kernel(const tp_filter *f);
 int tp_filter_get_hs(tp_filter *f, double *Hs);          /* [dev, own elements] */
 /* PDE filter (type 2): the 8x8 Helmholtz element matrix KF of PDEFilt::PDEFilterMatrix (PDEFilter.cc:472-576), host */
 int tp_filter_get_kf(const tp_filter *f, double *kf_host_64);

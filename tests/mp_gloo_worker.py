@@ -164,6 +164,9 @@ def gpu_mode(rank, world):
         ul = torch.from_numpy(ug[pl.global_slice(3)].copy()).cuda()
         yl = le.level_apply(l, ul).cpu().numpy()
         assert rel(yl[pl.owned_slice(3)], yg[pl.global_slice(3)][pl.owned_slice(3)]) <= 1e-12, l
+        if l == 0 and os.environ.get("TP_FINE_V"):     # a forced generation / tile of the fine kernel must be the one that launched
+            want = (1, int(os.environ["TP_FINE_V"])) + ((int(os.environ["TP_FINE_SHAPE"]),) if os.environ.get("TP_FINE_SHAPE") else ())
+            assert le.last_op_form()[:len(want)] == want, (le.last_op_form(), want)
         assert abs(le.level_lambda(l) / mg.lam(l) - 1) <= 1e-9
     # PDE filter on slabs
     pf = tp.Filter(grid, 2, 2.56 * h, tp.SolverOptions(nlvls=3, rtol=1e-8, dtol=1e3, max_it=60, nsmooth=2, ncoarse=10))

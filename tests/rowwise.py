@@ -1,0 +1,304 @@
+"""Row-wise error bounds for the operator kernels on 0/1 designs (a plain helper module: no fixtures, no collection hooks).
+
+Why: rel(a, b) = max|a - b| / max|b| measures every row against the LARGEST row.  With Emin = 1e-9, Emax = 1, p = 3 the rows
+of K(x) that touch only void elements are ~1e-9 of the largest ones, so a tolerance of 1e-13 max|y| leaves them unchecked
+beyond four digits -- and a converged design is exactly such a field.  Here every row i is held to
+
+    |got_i - ref_i| <= c * eps * scale_i,        eps = 2^-53,
+
+`ref` from the 80-bit arbiter (oracle/arbiter.py) and `scale_i` the sum of the absolute values of the terms that make up
+row i (a majorant of it, computed with the float64 oracle -- its own rounding, 1e-16 of itself, does not matter):
+
+    level 0      s = matfree_apply(KE -> max|KE| ones, E, N -> ones, |u|)  =  sum_{e in i} E_e max|KE| ||u_e||_1
+    level l > 0  S_l(v) = restrict(S_{l-1}(prolong(v))), v = |u|: P and R are non-negative, so this bounds |R A P| |u| and
+                 the rounding of the stored Galerkin coefficients alike
+    transfers    R |r|  and  |x_f| + P |x_c|
+    one Chebyshev step   |x0| + c dinv (|b| + S_l(|x0|)),  c = 1 / theta of the level's window
+    dfdx         p x^(p-1) (Emax - Emin) max|KE| ||u_e||_1^2   per element
+    cone filter  H'|x| / Hs + (H|x| / Hs) rho  with the majorant weights H' = H + (R + L) B (class Cone below: B the 0/1
+                 pattern of H, L the largest element-centre coordinate, rho = (R + L) B1 / Hs); gradients: the same on |df|
+
+THE CONSTANTS c come from the length of the chain of rounded operations of the form, never from what the HIP kernels
+achieve; beside each: the count, and what the float64 oracle measures against the arbiter on the CPU
+(tests/test_rowwise_oracle.py holds the oracle to a QUARTER of each, on every generator below).  Rule: the larger of the
+count and 16 x the measured value, rounded up to a power of two.
+"""
+import numpy as np
+
+EPS = 2.0 ** -53
+
+# ---- level 0 product (apply, apply_krylov, residual): 3 + 3 butterfly stages of the Walsh-Hadamard form, dot products of
+# at most 24 terms, the modulus scale, the 8-element nodal sum, ~5 eps of representation error of the packed form against
+# its double-double export: gamma ~ 50.  Oracle against arbiter, measured: 1.11 over the generators (x 16 = 18); 0.57
+# on the planted-error mesh.
+C_FINE = 64
+
+
+def c_level(l):
+    """stored / applied Galerkin level l >= 1.  Count: the row's dot product over 27 neighbours x 3 components (81), the nodal
+    sum over 8 coarse elements (8), and per Galerkin step l' <= l the two contractions of a child's 24 dofs with the
+    interpolation weights (24 + 24 additions; the weights are powers of two, their products exact) and the sum over the 8
+    children (8): 89 + 56 l -> 256 for l = 1, 2, 512 for l = 3, 4.  The reference hierarchy is the arbiter's Galerkin
+    product of KE; level 1 applied from the fine densities uses a packed tensor of KE's children, whose representation error
+    (~5 eps of max|KE|, as on level 0) is inside this count's slack (145 of 256).  Oracle against arbiter, measured: 5.24 (x 16 = 84)."""
+    return _pow2(89 + 56 * l)
+
+
+def c_diag(l):
+    """the Jacobi diagonal (exported as its reciprocal), RELATIVE to the row's own diagonal entry.  Count: level 0 the 8-element
+    sum of positive terms, the modulus scale, the reciprocal and the test's own division back: 11; level l the
+    coefficient's formation as in c_level (8 + 56 l) + 2: 66, 122, 178.  Oracle (assembled CSR) against arbiter, measured:
+    3.94 on level 0 (x 16 = 63 -> 64), 14.7 on levels 1, 2 (x 16 = 235 -> 256): the measured values set both."""
+    return 64 if l == 0 else max(256, _pow2(10 + 56 * l))
+
+
+# restriction: a coarse row gathers <= 27 fine nodes with power-of-two weights: 27 additions.  Measured: 3.26 (x 16 = 52 -> 64).
+C_RESTRICT = 64
+# prolongation + add: <= 8 coarse nodes, then the sum with x_f: 9.  Measured: 2.10 (x 16 = 34 -> 64).
+C_PROLONG = 64
+
+
+def c_smooth(l):
+    """one Chebyshev step x1 = x0 + (1/theta) dinv (b - A x0), the reference step formed in 80-bit arithmetic from the
+    DEVICE's dinv and window.  Count: the product's chain (C_FINE or c_level(l)'s count) + 1/theta, b - Ax, x dinv, x 1/theta,
+    + x0 (5); the fine level forms its Jacobi diagonal on the fly (8-element sum of positive terms + modulus scale +
+    reciprocal: 11) -> 50 + 16 = 66 -> 128 on level 0, 94 + 56 l -> 256 / 256 / 512 on levels 1 / 2 / 3.  Oracle against
+    arbiter, measured: 3.20 (x 16 = 51)."""
+    return _pow2(66) if l == 0 else _pow2(94 + 56 * l)
+
+
+# dfdx per element: u_e^T KE u_e as 24 dot products of 24 terms and a 24-term sum (48), pow(x, p - 1) (<= 2), three scale
+# factors (3): 53.  Measured: 6.91 (x 16 = 111 -> 128).
+C_DFDX = 128
+
+
+# the meshes of tests/test_gpu_rowwise.py (elements; COARSE_MESHES with their level count)
+# elements; nx = 15, 16, 17, 31, 32, 33, 62, 63 and ny = 7, 8, 9, 15, 16 (the seams of the 15-node and the 31 x 7 tiles and one plane
+# either side), 45 planes twice (more than the 43-plane chunk of the 32 x 8 tiles), and the two odd meshes of test_odd_sized_mesh_apply
+FILTER_MESH = (26, 22, 20)      # cone filter: ElemConn 10 needs 20 elements every way
+FILTER_RFACS = (1.5, 2.56, 5.12, 10.24)   # ElemConn 1, 2 (tiled), 5 (wide), 10 (streamed ring)
+FINE_MESHES = [(14, 6, 2), (15, 7, 3), (16, 8, 44), (30, 14, 7), (31, 15, 12), (32, 6, 9), (61, 8, 16), (62, 15, 44), (31, 17, 5), (33, 4, 2)]
+COARSE_MESHES = [((36, 28, 20), 3), ((40, 24, 16), 4)]
+
+
+def c_filter(conn):
+    """cone filter, forward and gradients.  Count: one fma chain over the (2 conn + 1)^3 window for H v, the same for Hs, the
+    division and the gradient forms' pre- / post-scalings (3): 2 (2 conn + 1)^3 + 3 -> conn 1: 57 -> 64, 2: 253 -> 256,
+    5: 2665 -> 4096, 10: 18525 -> 32768.  The chain is long, but every weight is non-negative: the scale is the size of the
+    row's own terms.  The weights R - dist cancel: the reference forms dist from element-centre COORDINATES (size <= L), so each
+    weight carries an absolute error of ~eps (R + L) whatever its size -- the scale's second term (Cone), not the constant.
+    Oracle against arbiter, measured: 1.11 (x 16 = 18) at conn 1, 2, 5."""
+    return _pow2(2 * (2 * conn + 1) ** 3 + 3)
+
+
+def _pow2(v):
+    return 1 << int(np.ceil(np.log2(v)))
+
+
+# =====================================================================================================================
+# 0/1 designs: x in {XMIN, 1}, deterministic, any mesh; element (i, j, k) at x[i + ex (j + ey k)]
+# =====================================================================================================================
+XMIN = 1e-3
+GENERATORS = ("blocks", "checker", "one_solid", "one_void", "zlayer")
+# node planes that carry block faces: the seams of the 15-node tiles (15, 30 -> 14..16, 30..32 with the tiles' overlap) and of
+# the 31 x 7 tiles (31; 7, 14), and one plane either side of them
+_FX = (13, 14, 15, 16, 17, 29, 30, 31, 32, 33)
+_FY = (5, 6, 7, 8, 9, 13, 14, 15, 16, 17)
+
+
+def design(kind, ex, ey, ez, kz=8):
+    """-> float64 array of ex ey ez densities; kz: z-chunk length of the kernel under test (node planes per chunk), or a tuple
+    of the lengths of several forms (product and Chebyshev step may chunk differently): a solid layer at every boundary"""
+    solid = np.zeros((ez, ey, ex), dtype=bool)
+    if kind == "blocks":
+        # block m: one with its LOW faces on the planes i = _FX[m], j = _FY[m], one with its HIGH faces there (they touch along
+        # an edge only), w = 2..4 elements wide, in a band of two element layers of its own
+        for m in range(len(_FX)):
+            w, k0 = 2 + m % 3, (2 * m) % max(ez, 1)
+            for (i0, i1), (j0, j1) in ((( _FX[m], _FX[m] + w), (_FY[m], _FY[m] + w)), ((_FX[m] - w, _FX[m]), (_FY[m] - w, _FY[m]))):
+                i0, i1, j0, j1 = max(i0, 0), min(i1, ex), max(j0, 0), min(j1, ey)
+                # a mesh that ends before the plane still gets the block against its last plane
+                if i0 >= i1:
+                    i0, i1 = max(ex - w, 0), ex
+                if j0 >= j1:
+                    j0, j1 = max(ey - w, 0), ey
+                solid[k0:k0 + 2, j0:j1, i0:i1] = True
+    elif kind == "checker":
+        k, j, i = np.meshgrid(np.arange(ez), np.arange(ey), np.arange(ex), indexing="ij")
+        lo = lambda n: n // 4
+        hi = lambda n: max(n // 4 + 1, n - n // 4)
+        region = (i >= lo(ex)) & (i < hi(ex)) & (j >= lo(ey)) & (j < hi(ey)) & (k >= lo(ez)) & (k < hi(ez))
+        solid = region & ((i + j + k) % 2 == 0)
+    elif kind == "one_solid":
+        solid[ez // 2, ey // 2, ex // 2] = True
+    elif kind == "one_void":
+        solid[:] = True
+        solid[ez // 2, ey // 2, ex // 2] = False
+    elif kind == "zlayer":
+        # the element layer whose lower node plane is the FIRST plane of a chunk: k = kz, 2 kz, ... (its upper plane is the chunk's
+        # second plane, the layer below it belongs to the chunk before); a mesh of one chunk: its last layer
+        kzs = kz if isinstance(kz, (tuple, list)) else (kz,)
+        ks = sorted({k for k in range(1, ez) for q in kzs if k % max(q, 1) == 0}) or [ez - 1]
+        solid[ks, :, :] = True
+    else:
+        raise ValueError(kind)
+    return np.where(solid, 1.0, XMIN).reshape(-1)
+
+
+# =====================================================================================================================
+# row scales
+# =====================================================================================================================
+def level_dims(nx, ny, nz, l):
+    return ((nx - 1) >> l) + 1, ((ny - 1) >> l) + 1, ((nz - 1) >> l) + 1
+
+
+def scale_fine(orc, nx, ny, nz, KE, E, u, N=None):
+    """sum over the elements of a row of E_e max|KE| ||u_e||_1 (N -> ones: a clamped neighbour only lowers the true sum).  With N:
+    a Dirichlet row carries |u| instead, the identity the operator has there -- what the coarser levels' Galerkin products see
+    of it (on level 0 itself those rows must return u bit for bit: the caller sets their scale to 0)"""
+    n = 3 * nx * ny * nz
+    kmax = np.full(576, float(np.abs(np.asarray(KE, dtype=np.float64)).max()))
+    au = np.abs(np.asarray(u, dtype=np.float64))
+    s = orc.matfree_apply(nx, ny, nz, 3, kmax, orc.f64(E), np.ones(n), au)
+    return s if N is None else np.where(np.asarray(N) != 0, s, au)
+
+
+def scale_level(orc, mg, l, dims, KE, E, N, u):
+    """S_l(|u|) = R_{l-1} ... R_0 S_0(P_0 ... P_{l-1} |u|); mg: an assembled orc.MG of the same mesh (its transfers are used)"""
+    v = np.abs(np.asarray(u, dtype=np.float64))
+    for m in range(l - 1, -1, -1):
+        v = mg.prolong(m, v)
+    s = scale_fine(orc, *dims, KE, E, v, N)
+    for m in range(l):
+        s = mg.restrict(m, s)
+    return s
+
+
+def scale_restrict(mg, l, rf):
+    return mg.restrict(l, np.abs(np.asarray(rf, dtype=np.float64)))
+
+
+def scale_prolong_add(mg, l, xc, xf):
+    return np.abs(np.asarray(xf, dtype=np.float64)) + mg.prolong(l, np.abs(np.asarray(xc, dtype=np.float64)))
+
+
+def scale_smooth(s_x0, dinv, inv_theta, b, x0):
+    """|x0| + c dinv (|b| + S_l(|x0|)); s_x0 = S_l(|x0|) (zeros for a zero guess)"""
+    return np.abs(x0) + inv_theta * np.abs(dinv) * (np.abs(b) + s_x0)
+
+
+def elem_u1(nx, ny, nz, U):
+    """||u_e||_1 per element"""
+    a = np.abs(np.asarray(U, dtype=np.float64)).reshape(nz, ny, nx, 3).sum(-1)
+    s = np.zeros((nz - 1, ny - 1, nx - 1))
+    for dk in (0, 1):
+        for dj in (0, 1):
+            for di in (0, 1):
+                s += a[dk:nz - 1 + dk, dj:ny - 1 + dj, di:nx - 1 + di]
+    return s.reshape(-1)
+
+
+def scale_dfdx(nx, ny, nz, KE, U, x, Emin=1e-9, Emax=1.0, penal=3.0):
+    return penal * np.asarray(x, dtype=np.float64) ** (penal - 1) * (Emax - Emin) * float(np.abs(KE).max()) * elem_u1(nx, ny, nz, U) ** 2
+
+
+class Cone:
+    """The cone filter's matrix in numpy, for the row scales: H (weights R - dist < R, dist from the integer offsets), its 0/1
+    pattern B (dist < R (1 + 1e-12): a weight that one side rounds to zero and the other does not is below eps R either way), and
+    the majorant H' = H + (R + L) B -- every weight plus the absolute error eps (R + L) it can carry (c_filter's docstring)."""
+
+    def __init__(self, ex, ey, ez, h, R, conn):
+        self.shape, self.conn, self.R = (ez, ey, ex), conn, R
+        hx, hy, hz = (h, h, h) if np.isscalar(h) else h
+        self.L = max(ex * hx, ey * hy, ez * hz)
+        self.taps = []
+        for dk in range(-conn, conn + 1):
+            for dj in range(-conn, conn + 1):
+                for di in range(-conn, conn + 1):
+                    dist = np.sqrt((di * hx) ** 2 + (dj * hy) ** 2 + (dk * hz) ** 2)
+                    if dist < R * (1 + 1e-12):
+                        self.taps.append((dk, dj, di, max(R - dist, 0.0)))
+        one = np.ones(ex * ey * ez)
+        self.Hs, self.n = self.H(one), self.B(one)
+        self.rho = (R + self.L) * self.n / self.Hs
+
+    def _conv(self, v, weight):
+        c, (ez, ey, ex) = self.conn, self.shape
+        p = np.zeros((ez + 2 * c, ey + 2 * c, ex + 2 * c))
+        p[c:c + ez, c:c + ey, c:c + ex] = np.asarray(v, dtype=np.float64).reshape(self.shape)
+        out = np.zeros(self.shape)
+        for dk, dj, di, w in self.taps:
+            out += weight(w) * p[c + dk:c + dk + ez, c + dj:c + dj + ey, c + di:c + di + ex]
+        return out.reshape(-1)
+
+    def H(self, v):
+        return self._conv(v, lambda w: w)
+
+    def B(self, v):
+        return self._conv(v, lambda w: 1.0)
+
+    def M(self, v):
+        return self._conv(v, lambda w: w + self.R + self.L)
+
+    def scale_forward(self, ftype, x):
+        """type 1: x~ = H x / Hs; type 0 copies x: scale 0, i.e. bit for bit"""
+        ax = np.abs(x)
+        return self.M(ax) / self.Hs + self.H(ax) / self.Hs * self.rho if ftype == 1 else np.zeros(ax.size)
+
+    def scale_gradient(self, ftype, x, df):
+        """type 1: H (df / Hs); type 0: (H (df x) / Hs) / max(1e-3, x), the reference's divisor"""
+        x, adf = np.asarray(x, dtype=np.float64), np.abs(df)
+        if ftype == 1:
+            g = adf / self.Hs
+            return self.M(g) + self.H(g * self.rho)
+        v = adf * np.abs(x)
+        return (self.M(v) / self.Hs + self.H(v) / self.Hs * self.rho) / np.maximum(1e-3, x)
+
+
+# =====================================================================================================================
+# the assertion
+# =====================================================================================================================
+def rel(a, b):
+    """the suite's older metric (tests/test_gpu_parity.py), kept here for the planted-error test"""
+    return np.abs(a - b).max() / max(np.abs(b).max(), 1e-300)
+
+
+def achieved(got, ref_ld, scale):
+    """max_i |got - ref|_i / (eps scale_i) over the rows with scale > 0 (0.0 if there are none)"""
+    d = np.abs(np.asarray(got, dtype=np.longdouble) - np.asarray(ref_ld, dtype=np.longdouble)).astype(np.float64)
+    pos = scale > 0
+    return float((d[pos] / (EPS * scale[pos])).max()) if pos.any() else 0.0
+
+
+def _describe(row, where):
+    nx, ny, nz = where["dims"]
+    dof, kz = where.get("dof", 3), where.get("kz", 0)
+    n, c = (row // dof, row % dof) if dof else (row, -1)
+    i, j, k = n % nx, (n // nx) % ny, n // (nx * ny)
+    what = "node" if dof else "element"
+    return ("%s (%d, %d, %d)%s, i mod 15 = %d, i mod 31 = %d, j mod 7 = %d, plane offset in its z-chunk (kz %s) = %s"
+            % (what, i, j, k, " component %d" % c if dof else "", i % 15, i % 31, j % 7, kz or "-", (k - where.get("k0", 0)) % kz if kz else "-"))
+
+
+def assert_rowwise(got, ref_ld, scale, c, where):
+    """fails if |got - ref|_i > c eps scale_i for ANY row i; rows with scale == 0 must match exactly.  where: {"label": the kernel
+    form and case, "dims": (nx, ny, nz) of the level (element counts for element vectors), "dof": 3 / 1 / 0 (0: element
+    vector), "kz": z-chunk length of the form (0: none), "k0": first plane of the chunking}.  -> the achieved c"""
+    got = np.asarray(got)
+    scale = np.asarray(scale, dtype=np.float64)
+    assert got.shape == scale.shape == np.asarray(ref_ld).shape, (where.get("label"), got.shape, scale.shape, np.asarray(ref_ld).shape)
+    assert np.isfinite(got).all() and np.isfinite(scale).all() and (scale >= 0).all(), where.get("label")
+    d = np.abs(got.astype(np.longdouble) - np.asarray(ref_ld, dtype=np.longdouble)).astype(np.float64)
+    zero = scale == 0
+    if (d[zero] != 0).any():
+        row = int(np.flatnonzero(zero & (d != 0))[0])
+        raise AssertionError("%s: row %d has scale 0 and must match exactly, |got - ref| = %.3e (%d such rows); %s"
+                             % (where.get("label"), row, d[row], int((d[zero] != 0).sum()), _describe(row, where)))
+    ratio = np.zeros_like(d)
+    ratio[~zero] = d[~zero] / (EPS * scale[~zero])
+    row = int(np.argmax(ratio))
+    if ratio[row] > c:
+        raise AssertionError("%s: %d of %d rows beyond %g eps scale; worst: row %d, achieved c = %.4g (|got - ref| = %.3e, scale = %.3e, "
+                             "scale / max scale = %.1e); %s" % (where.get("label"), int((ratio > c).sum()), ratio.size, c, row, ratio[row],
+                                                                d[row], scale[row], scale[row] / scale.max(), _describe(row, where)))
+    return float(ratio[row])

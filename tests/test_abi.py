@@ -80,8 +80,11 @@ SWITCHES_SET_BY_NAME = {
                                   "TP_DEBUG_SYNC"],
     "tests/test_gpu_parity.py": ["TP_TEST_FORCE_GIVEUP", "TP_NO_COARSE_DIRECT", "TP_NO_COARSE_XCD", "TP_NO_LANCZOS_XCD",
                                  "TP_CD_INVERT_COLUMNS", "TP_NO_FILTER_TILE", "TP_FILTER_ZMULTI", "TP_NO_REDUCE_TAIL"],
-    "tests/test_multirank.py": ["TP_REPLICATE_FROM", "TP_TEST_FORCE_GIVEUP"],
-    "tests/mp_gloo_worker.py": ["TP_OVERLAP", "TP_TEST_FORCE_GIVEUP"],
+    "tests/test_multirank.py": ["TP_REPLICATE_FROM", "TP_TEST_FORCE_GIVEUP", "TP_FINE_V", "TP_FINE_SHAPE"],
+    "tests/test_gpu_rowwise.py": ["TP_FINE_V", "TP_FINE_SHAPE", "TP_TILE_KZ", "TP_NO_TILE", "TP_NO_MACRO", "TP_NO_CORR_FUSE", "TP_DIA_SPLIT",
+                                  "TP_DIA_NODE", "TP_NO_DIA_SYM", "TP_MACRO_KZ", "TP_FILTER_ZMULTI", "TP_NO_FILTER_TILE"],
+    "tests/rowwise_worker.py": ["TP_MACRO_KZ"],
+    "tests/mp_gloo_worker.py": ["TP_OVERLAP", "TP_TEST_FORCE_GIVEUP", "TP_FINE_V", "TP_FINE_SHAPE"],
     "tools/fine_ab.py": ["TP_FINE_V", "TP_TILE_KZ"],
     "tools/r06_c3_hist_variants.py": ["TP_DIA_NODE", "TP_NO_DIA_SYM"],
     "tools/r06_filter_ab.py": ["TP_FILTER_ZMULTI"],

@@ -150,6 +150,18 @@ def test_coarse_levels_replicated_on_every_rank(nproc, mesh, env):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("shape", ["1", "2"])
+@pytest.mark.parametrize("nproc,mesh", [(2, (32, 16, 64, 5, 2, 20, "1,3,1,1")), (4, (20, 12, 32, 3))])
+def test_third_generation_fine_kernel_on_slabs(nproc, mesh, shape):
+    """The third-generation fine kernel (k_fine_u4; 16x16 tiles: TP_FINE_SHAPE=1, 32x8: 2) is what every rank of the 8-GPU
+    geometries of C3 and C5 runs (171 tiles of 32x8 at nx = 257, ny = 129; threshold 160), with the boundary-first split
+    passes, the one-plane ranges r1lo / r1hi, ghost planes and own_lo > 0 -- forced here on slab meshes small enough for the
+    serial oracle: iteration count, history, U, objective, sensitivities, every level operator; overlapped = blocking halos
+    bitwise (tests/mp_gloo_worker.py, which also asserts that generation 3 with that tile is what launched)."""
+    _launch("gpu", nproc=nproc, timeout=600, extra=mesh, env_extra={"TP_FINE_V": "3", "TP_FINE_SHAPE": shape})
+
+
+@pytest.mark.gpu
 def test_replicated_levels_take_their_halo_exchanges_out():
     """the point of the replicated sub-hierarchy: with levels 2-4 on every rank the solve issues far fewer halo exchanges than
     with the coarsest level only (same mesh, same cycle, same iteration count -- both runs are checked against the oracle)"""

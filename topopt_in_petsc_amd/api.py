@@ -487,6 +487,14 @@ class LinearElasticity:
         self.L.tp_elasticity_last_stats(self.handle, C.byref(b), C.byref(f), C.byref(n))
         return b.value, f.value, n.value
 
+    def last_op_form(self):
+        """(kind, a, b, c) of the last operator application (tp_elasticity_last_op_form): kind 1 fine tile kernel (generation,
+        tile 0 15x15 / 1 16x16 / 2 32x8, z-chunk), 2 level 1 from the fine densities (correction fused, -, z-chunk), 3 per-node
+        matrix-free, 4 stored stencil (threads per row, node form, mirrored reads)"""
+        f = (C.c_int * 4)()
+        _chk(self.L.tp_elasticity_last_op_form(self.handle, f), "tp_elasticity_last_op_form")
+        return tuple(f)
+
 
 class Filter:
     """Filter (Filter.h:34-92): filterType 0 sensitivity, 1 density, 2 PDE."""
@@ -514,6 +522,10 @@ class Filter:
     @property
     def ElemConn(self):
         return self.L.tp_filter_stencil_width(self.handle)
+
+    def last_kernel(self):
+        """cone-filter kernel of the last convolution: 1 tiled, 2 several outputs along z, 3 wide, 4 streamed ring, 5 generic"""
+        return self.L.tp_filter_last_kernel(self.handle)
 
     def Hs(self):
         hs = self.grid.elem_vec()

@@ -358,6 +358,7 @@ struct tp_filter {
     int last_its;
     double last_rnorm;
     long violations;
+    int last_kernel = 0;  // cone filter kernel of the last convolution (tp_filter_last_kernel): 1 tiled, 2 several outputs along z, 3 wide, 4 streamed ring, 5 generic
 };
 
 static int filter_conv(tp_filter *f, double *out, const double *d1, const double *d2) {
@@ -369,11 +370,17 @@ static int filter_conv(tp_filter *f, double *out, const double *d1, const double
     const dim3 tg((g->ex + 31) / 32, (g->ey + 3) / 4, (g->ez_own + 1) / 2);
     const bool no_tile = sw_no_filter_tile();
 #define TP_CONV_TILED(CC)                                                                                            \
+    do {  \
     TP_LAUNCH(k_conv_filter_tiled<CC>, tg, dim3(256), 0, g->stream, g->ex, g->ey, g->ez_own, g->rank * g->ez_own, \
-                       g->ez_glob, f->xg, f->wtab, out, d1, d2)
+                       g->ez_glob, f->xg, f->wtab, out, d1, d2);                                                         \
+    f->last_kernel = 1;  \
+    } while (0)
 #define TP_CONV_WIDE(CC, TYE, TZE)                                                                                                   \
+    do {  \
     TP_LAUNCH((k_conv_filter_wide<CC, TYE, TZE>), dim3((g->ex + 31) / 32, (g->ey + TYE - 1) / TYE, (g->ez_own + TZE - 1) / TZE), \
-              dim3(8 * TYE * TZE), 0, g->stream, g->ex, g->ey, g->ez_own, g->rank * g->ez_own, g->ez_glob, f->xg, f->wtab, out, d1, d2)
+              dim3(8 * TYE * TZE), 0, g->stream, g->ex, g->ey, g->ez_own, g->rank * g->ez_own, g->ez_glob, f->xg, f->wtab, out, d1, d2); \
+    f->last_kernel = 3;  \
+    } while (0)
     // Round 6 (counters: the one-output form is LDS-issue bound, one ds_read per fma): the four-outputs-per-thread form was
     // measured for the small radii too, bit-equal -- ElemConn 3 (343 taps): 105.5 -> 69.8 us at 128^3, taken; ElemConn 2 (125
     // taps, the bench's 2.56 h): 96 us against 50 (its 32-byte lane stride of the staged rows conflicts in the LDS banks, and a
@@ -386,8 +393,11 @@ static int filter_conv(tp_filter *f, double *out, const double *d1, const double
     const long wgs1 = (long)tg.x * tg.y * tg.z;
     const int zm = zm_env >= 0 ? zm_env : (wgs1 >= 8192 ? 4 : (wgs1 >= 1024 ? 2 : 0));
 #define TP_CONV_ZMULTI(CC, NO)                                                                                                     \
+    do {  \
     TP_LAUNCH((k_conv_filter_zmulti<CC, NO>), dim3((g->ex + 31) / 32, (g->ey + 3) / 4, (g->ez_own + 2 * NO - 1) / (2 * NO)), dim3(256), 0, \
-              g->stream, g->ex, g->ey, g->ez_own, g->rank * g->ez_own, g->ez_glob, f->xg, f->wtab, out, d1, d2)
+              g->stream, g->ex, g->ey, g->ez_own, g->rank * g->ez_own, g->ez_glob, f->xg, f->wtab, out, d1, d2);                 \
+    f->last_kernel = 2;  \
+    } while (0)
     if (!no_tile && c == 2 && zm == 4)
         TP_CONV_ZMULTI(2, 4);
     else if (!no_tile && c == 2 && zm == 2)
@@ -413,8 +423,11 @@ static int filter_conv(tp_filter *f, double *out, const double *d1, const double
 #undef TP_CONV_WIDE
 #undef TP_CONV_ZMULTI
 #define TP_CONV_ZRING(CC)                                                                                                             \
+    do {  \
     TP_LAUNCH((k_conv_filter_zring<CC>), dim3((g->ex + 31) / 32, (g->ey + 15) / 16, (g->ez_own + 3) / 4), dim3(256), 0, g->stream, \
-              g->ex, g->ey, g->ez_own, g->rank * g->ez_own, g->ez_glob, f->xg, f->wtab, out, d1, d2)
+              g->ex, g->ey, g->ez_own, g->rank * g->ez_own, g->ez_glob, f->xg, f->wtab, out, d1, d2);                              \
+    f->last_kernel = 4;  \
+    } while (0)
     else if (!no_tile && c == 9)
         TP_CONV_ZRING(9);
     else if (!no_tile && c == 10)
@@ -448,9 +461,11 @@ static int filter_conv(tp_filter *f, double *out, const double *d1, const double
     else if (!no_tile && c == 24)
         TP_CONV_ZRING(24);
 #undef TP_CONV_ZRING
-    else
+    else {
         TP_LAUNCH(k_conv_filter, dim3((int)((f->nel + BLK - 1) / BLK)), dim3(BLK), 0, g->stream, g->ex, g->ey,
                            g->ez_own, c, g->rank * g->ez_own, g->ez_glob, f->xg, f->wtab, out, d1, d2);
+        f->last_kernel = 5;
+    }
 #undef TP_CONV_TILED
     const double w3 = (2.0 * c + 1) * (2.0 * c + 1) * (2.0 * c + 1);
     count_launch(g, (16.0 + (d1 ? 8.0 : 0.0) + (d2 ? 8.0 : 0.0)) * f->nel, 2.0 * w3 * f->nel);
@@ -650,6 +665,7 @@ extern "C" int tp_filter_destroy(tp_filter *f) {
     return TP_OK;
 }
 extern "C" int tp_filter_stencil_width(const tp_filter *f) { return f->conn; }
+extern "C" int tp_filter_last_kernel(const tp_filter *f) { return f ? f->last_kernel : 0; }
 extern "C" int tp_filter_get_kf(const tp_filter *f, double *kf_host_64) {
     if (!f || !kf_host_64 || f->type != 2 || f->KF.size() < 64) return TP_ERR_ARG;
     std::memcpy(kf_host_64, f->KF.data(), sizeof(double) * 64);

@@ -173,6 +173,7 @@ int MGSolver<DOF>::op_fine(OpLaunch &c, const NodeArgs &a) {
             else TP_LAUNCH((k_matfree_tile<EPI, 0>), gdim, dim3(TILE * TILE), 0, grid->stream, ta, a);
         }
         if (c.split && pass == 0) TP_TRY(after_boundary(c.l, a.out));
+        last_form[0] = 1, last_form[1] = gen, last_form[2] = wide ? (shape_env == 3 ? 3 : 2) : (gen == 3 ? 1 : 0), last_form[3] = kz;
     }
     if (timed) kernel_timer_mark(grid);
     c.bytes = 16.0 * DOF * c.nown + 8.0 * L.g.own_elems();
@@ -226,6 +227,7 @@ int MGSolver<DOF>::op_macro(OpLaunch &c, const NodeArgs &a) {
         TP_LAUNCH((k_matfree_tile<EPI, 1>), dim3(tx, ty, tz), dim3(TILE * TILE), 0, grid->stream, ta, a);
         if (c.split && pass == 0) TP_TRY(after_boundary(c.l, a.out));
     }
+    last_form[0] = 2, last_form[1] = fuse_corr ? 1 : 0, last_form[2] = 0, last_form[3] = kz;
     if (fuse_corr) {
         if constexpr (EPI != EPI_APPLY_DOT) {
             TP_LAUNCH((k_macro_corr_apply<EPI>), dim3((L.ncorr_nodes + BLK - 1) / BLK), dim3(BLK), 0, grid->stream,
@@ -260,6 +262,7 @@ int MGSolver<DOF>::op_matfree_node(OpLaunch &c, const NodeArgs &a) {
         c.bytes = 16.0 * DOF * c.nown + (L.E ? 8.0 * L.g.own_elems() : 0.0);
         c.flops = 2.0 * (8 * DOF) * (8 * DOF) * (double)L.g.own_elems();
     }
+    last_form[0] = 3, last_form[1] = last_form[2] = last_form[3] = 0;
     return TP_OK;
 }
 
@@ -290,29 +293,37 @@ int MGSolver<DOF>::op_stencil(OpLaunch &c, const NodeArgs &a) {
         if (rsplit == 9) {
             nbr = (int)((rows + BLK / 9 - 1) / (BLK / 9));
             TP_LAUNCH((k_dia_row_split<DOF, EPI, 9>), dim3(nbr), dim3(BLK), 0, grid->stream, o, a);
+            last_form[0] = 4, last_form[1] = 9, last_form[2] = 0, last_form[3] = 0;
         } else if (rsplit == 3) {
             // round 6: a thread per node and z-offset (k_dia_node3: the same bits, a third of the waves); TP_DIA_NODE=0: per row
             bool done = false;
             if constexpr (DOF == 3) {
                 if (by_node && EPI != EPI_APPLY_DOT) {
                     nbr = (int)((rows / 3 + 63) / 64);
-                    if (sym)
+                    if (sym) {
                         TP_LAUNCH((k_dia_node3<EPI, true>), dim3(nbr), dim3(192), 0, grid->stream, o, a);
-                    else
+                        last_form[0] = 4, last_form[1] = 3, last_form[2] = 1, last_form[3] = 1;
+                    } else {
                         TP_LAUNCH((k_dia_node3<EPI, false>), dim3(nbr), dim3(192), 0, grid->stream, o, a);
+                        last_form[0] = 4, last_form[1] = 3, last_form[2] = 1, last_form[3] = 0;
+                    }
                     done = true;
                 }
             }
             if (!done) {
                 nbr = (int)((rows + BLK / 3 - 1) / (BLK / 3));
-                if (sym)
+                if (sym) {
                     TP_LAUNCH((k_dia_row_split<DOF, EPI, 3, true>), dim3(nbr), dim3(BLK), 0, grid->stream, o, a);
-                else
+                    last_form[0] = 4, last_form[1] = 3, last_form[2] = 0, last_form[3] = 1;
+                } else {
                     TP_LAUNCH((k_dia_row_split<DOF, EPI, 3>), dim3(nbr), dim3(BLK), 0, grid->stream, o, a);
+                    last_form[0] = 4, last_form[1] = 3, last_form[2] = 0, last_form[3] = 0;
+                }
             }
         } else {
             nbr = (int)((rows + BLK - 1) / BLK);
             TP_LAUNCH((k_dia_row<DOF, EPI>), dim3(nbr), dim3(BLK), 0, grid->stream, o, a);
+            last_form[0] = 4, last_form[1] = 1, last_form[2] = 0, last_form[3] = 0;
         }
         last_nblocks = nbr;
         return TP_OK;

@@ -1457,6 +1457,11 @@ extern "C" int tp_elasticity_last_stats(const tp_elasticity *e, double *alg_byte
     e->grid->launches = 0;
     return TP_OK;
 }
+extern "C" int tp_elasticity_last_op_form(const tp_elasticity *e, int *form4) {
+    if (!e || !form4) return TP_ERR_ARG;
+    for (int i = 0; i < 4; i++) form4[i] = e->mg.last_form[i];
+    return TP_OK;
+}
 
 // ===========================================================================
 // density / sensitivity filter and Helmholtz PDE filter

@@ -120,9 +120,11 @@ SYMBOLS = {
     "tp_elasticity_restrict": (_i, [_vp, _i, _vp, _vp]),
     "tp_elasticity_prolong_add": (_i, [_vp, _i, _vp, _vp]),
     "tp_elasticity_last_stats": (_i, [_vp, C.POINTER(_d), C.POINTER(_d), C.POINTER(_l)]),
+    "tp_elasticity_last_op_form": (_i, [_vp, C.POINTER(_i)]),
     "tp_filter_create": (_i, [C.POINTER(_vp), _vp, _i, _d, C.POINTER(SolverOpts)]),
     "tp_filter_destroy": (_i, [_vp]),
     "tp_filter_stencil_width": (_i, [_vp]),
+    "tp_filter_last_kernel": (_i, [_vp]),
     "tp_filter_get_hs": (_i, [_vp, _vp]),
     "tp_filter_get_kf": (_i, [_vp, _vp]),
     "tp_filter_project": (_i, [_vp, _vp, _vp, _vp, _i, _d, _d]),
