@@ -258,6 +258,24 @@ int tp_elasticity_objective_only(tp_elasticity *e, const double *U, const double
  * dgdx = 1/n (may be NULL) of the state U as it is -- no solve, no reduction, no host synchronisation. */
 int tp_elasticity_sensitivities(tp_elasticity *e, const double *U, const double *xPhys, double Emin, double Emax,
                                 double penal, double *dfdx, double *dgdx);
+/* Several load cases on one design: the weighted response  sum_l w_l sum_e E_e v_l^T KE u_l  and its sensitivity,
+ * all cases in ONE pass over the elements (xPhys read once, dfdx written once, one reduction and one host
+ * synchronisation for all sums).  V_l = U_l is the compliance of case l; V_l an adjoint state gives the sensitivity of
+ * any linear response of U_l.  Pointer convention of tp_mma_update's dgdx: host arrays of device pointers.  The ghost
+ * planes of every distinct vector are refreshed first.  With fx, gx and f_case all NULL nothing is reduced and the host
+ * does not wait (tp_elasticity_sensitivities' contract).  ncase = 1, V = w = NULL: tp_elasticity_objective's dfdx bit
+ * for bit; its fx to rounding (x^p is formed as x^(p-1) x).  TP_ERR_ARG unless 1 <= ncase <= TP_MAX_CASES and e, U,
+ * xPhys and every U[l] are given. */
+#define TP_MAX_CASES 8
+int tp_elasticity_response(tp_elasticity *e, int ncase,
+        const double *const *U,   /* host array of ncase [dev] pointers, local nodes*3 each            */
+        const double *const *V,   /* same; NULL, or an entry NULL: V_l = U_l (compliance)              */
+        const double *w,          /* host, ncase weights; NULL = all 1                                  */
+        const double *xPhys, double Emin, double Emax, double penal, double volfrac,
+        double *f_case,           /* host, ncase: f_l = sum_e E_e v_l^T KE u_l, UNWEIGHTED; may be NULL */
+        double *fx, double *gx,   /* fx = sum_l w_l f_l ; gx as tp_elasticity_objective; may be NULL    */
+        double *dfdx,             /* [dev] -p x^(p-1) (Emax-Emin) sum_l w_l v_l^T KE u_l ; may be NULL  */
+        double *dgdx);            /* [dev] 1/n ; may be NULL                                            */
 /* introspection for parity tests */
 /* KSPSetTolerances (LinearElasticity.cc:646); a negative value keeps the current one (PETSC_DEFAULT) */
 int tp_elasticity_set_tolerances(tp_elasticity *le, double rtol, double atol, double dtol, int max_it);

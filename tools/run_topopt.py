@@ -1,18 +1,46 @@
 #!/usr/bin/env python
 """End-to-end run of the reference's optimisation loop on the MI355X path.
-usage: run_topopt.py ex ey ez nlvls n_iter [filter [nsmooth ncoarse]]   (e.g. 128 128 128 5 20 1 2 45: the cycle of bench.py)"""
+usage: run_topopt.py [--loadcase top[:weight]]... ex ey ez nlvls n_iter [filter [nsmooth ncoarse]]
+(e.g. 128 128 128 5 20 1 2 45: the cycle of bench.py; --loadcase top:0.5 adds the line load on the upper edge as a second load
+case of weight 0.5 -- the objective becomes the weighted sum of the cases' compliances)"""
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import topopt_in_petsc_amd as tp
 
+
+def _loadcases(argv):
+    """takes every `--loadcase name[:weight]` / `--loadcase=name[:weight]` out of argv -> [(name, weight)]"""
+    cases, rest, i = [], [], 0
+    while i < len(argv):
+        a = argv[i]
+        if a == "--loadcase" or a.startswith("--loadcase="):
+            if a == "--loadcase":
+                i += 1
+                if i >= len(argv):
+                    sys.exit("--loadcase needs a value: top[:weight]")
+            v = argv[i] if a == "--loadcase" else a.split("=", 1)[1]
+            name, _, wt = v.partition(":")
+            if name != "top":
+                sys.exit("--loadcase: the only built-in further load case is 'top', got %r" % name)
+            cases.append((name, float(wt) if wt else 1.0))
+        else:
+            rest.append(a)
+        i += 1
+    return cases, rest
+
+
+loadcases, sys.argv[1:] = _loadcases(sys.argv[1:])
 ex, ey, ez, nlv, nit = [int(v) for v in sys.argv[1:6]]
 flt = int(sys.argv[6]) if len(sys.argv) > 6 else 1
 h = 1.0 / ey
 opt = tp.TopOpt(nxyz=(ex + 1, ey + 1, ez + 1), xc=(0, ex * h, 0, 1, 0, ez * h), nlvls=nlv, rmin=2.56 * h, filter=flt,
+                loadcases=loadcases or None,
                 solver=tp.SolverOptions(nlvls=nlv, **(dict(nsmooth=int(sys.argv[7]), ncoarse=int(sys.argv[8])) if len(sys.argv) > 8 else {})))
 print("# %dx%dx%d elements, %d DOF, %d MG levels, filter %d, rmin %.4f" % (ex, ey, ez, 3 * (ex + 1) * (ey + 1) * (ez + 1), nlv, flt, 2.56 * h))
 for it in range(nit):
     r = opt.step(verbose=True)
     print("State solver:  iter: %i, rerr.: %e | MMA inner its: %d" % (r["ksp_its"], r["ksp_rerr"], r["mma_inner"]), flush=True)
+    if "f_case" in r:
+        print("Load cases:    f: %s | iter: %s" % (" ".join("%e" % f for f in r["f_case"]), " ".join("%d" % k for k in r["ksp_its_case"])), flush=True)

@@ -274,6 +274,11 @@ class LinearElasticity:
         self.RHS = grid.node_vec(3)
         self.N = grid.node_vec(3)
         self.last_its, self.last_rnorm, self.last_bnorm, self.last_hist = 0, 0.0, 0.0, None
+        # load cases: case 0 is RHS / U above; AddLoadCase appends (RHS_l, U_l) -- every case keeps its own state, so
+        # each warm-starts from its own previous solution.  The supports N are shared.
+        self._case_rhs, self._case_U, self.case_weight = [self.RHS], [self.U], [1.0]
+        self.case_its, self.case_rnorm, self.case_bnorm = [0], [0.0], [0.0]
+        self.last_f_case = None
 
     def close(self):
         if getattr(self, "handle", None):
@@ -336,6 +341,47 @@ class LinearElasticity:
         R[top, ny - 1, 0, 2] = 0.5 * load
         self.SetBC(N.reshape(-1).to(self.U.device), R.reshape(-1).to(self.U.device))
 
+    def SetUpLoadAndBC_Top(self, weight=1.0):
+        """A second built-in right-hand side for the cantilever, added as a new load case (the supports N stay as they
+        are): line load +0.001 in z along the edge x = xmax, z = zmax, half loads at the two end nodes.  Single rank or
+        z-slabs (global z index decides).  Returns the index of the case."""
+        p = self.grid.part
+        nx, ny, nzl = p.nx, p.ny, p.nz_local
+        R = torch.zeros(nzl, ny, nx, 3, dtype=torch.float64)
+        top = (torch.arange(nzl) + p.node_z0) == p.nz - 1
+        R[top, :, nx - 1, 2] = 0.001
+        R[top, 0, nx - 1, 2] = 0.0005
+        R[top, ny - 1, nx - 1, 2] = 0.0005
+        return self.AddLoadCase(R.reshape(-1).to(self.U.device), weight)
+
+    # ---- several load cases on the shared supports N ----
+    @property
+    def ncases(self):
+        return len(self._case_rhs)
+
+    def AddLoadCase(self, RHS, weight=1.0):
+        """a further right-hand side (local node layout of self.RHS) with a persistent state of its own, zero at first;
+        returns its index.  At most TP_MAX_CASES cases, case 0 (self.RHS / self.U) included."""
+        if self.ncases >= _lib.MAX_CASES:
+            raise TopOptError(1, "AddLoadCase (more than TP_MAX_CASES = %d load cases)" % _lib.MAX_CASES)
+        rhs = self.grid.node_vec(3)
+        rhs.copy_(RHS)
+        self._case_rhs.append(rhs)
+        self._case_U.append(self.grid.node_vec(3))
+        self.case_weight.append(float(weight))
+        for lst, zero in ((self.case_its, 0), (self.case_rnorm, 0.0), (self.case_bnorm, 0.0)):
+            lst.append(zero)
+        return self.ncases - 1
+
+    def SetLoadCaseWeight(self, case, weight):
+        self.case_weight[case] = float(weight)
+
+    def LoadCaseRHS(self, case):
+        return self._case_rhs[case]
+
+    def LoadCaseU(self, case):
+        return self._case_U[case]
+
     def SetBC(self, N, RHS):
         self.N.copy_(N)
         self.RHS.copy_(RHS)
@@ -356,24 +402,44 @@ class LinearElasticity:
         _chk(self.L.tp_elasticity_apply_krylov(self.handle, _ptr(u), _ptr(y)), "tp_elasticity_apply_krylov")
         return y
 
-    def KSPSolve(self, hist_cap=0):
+    def KSPSolve(self, hist_cap=0, case=0):
+        """solve load case `case` on the last assembly, warm-started from that case's own state"""
         import numpy as np
+        RHS, U = self._case_rhs[case], self._case_U[case]
         its, rn, bn = C.c_int(), C.c_double(), C.c_double()
         hist = np.zeros(max(hist_cap, 1))
         import time
         t0 = time.perf_counter()   # the solve ends with a host read of ||r||: wall time == device time
-        rc = self.L.tp_elasticity_solve(self.handle, _ptr(self.RHS), _ptr(self.U), C.byref(its), C.byref(rn),
+        rc = self.L.tp_elasticity_solve(self.handle, _ptr(RHS), _ptr(U), C.byref(its), C.byref(rn),
                                         C.byref(bn), hist.ctypes.data if hist_cap else None, hist_cap)
         self.last_solve_s = time.perf_counter() - t0
         self.last_its, self.last_rnorm, self.last_bnorm = its.value, rn.value, bn.value
         self.last_hist = hist[: min(its.value + 1, hist_cap)] if hist_cap else None
+        self.case_its[case], self.case_rnorm[case], self.case_bnorm[case] = its.value, rn.value, bn.value
         _chk(rc, "tp_elasticity_solve")
         return its.value
 
     def SolveState(self, xPhys, Emin, Emax, penal, hist_cap=0):
-        """LinearElasticity.cc:182-223"""
+        """LinearElasticity.cc:182-223; several load cases: one assembly, then every case in index order"""
         self.AssembleStiffnessMatrix(xPhys, Emin, Emax, penal)
-        return self.KSPSolve(hist_cap)
+        its = self.KSPSolve(hist_cap)
+        for case in range(1, self.ncases):
+            its = self.KSPSolve(hist_cap, case)
+        return its
+
+    def Response(self, U_list, V_list, w, xPhys, Emin, Emax, penal, volfrac, dfdx=None, dgdx=None, sums=True):
+        """tp_elasticity_response: fx = sum_l w_l f_l with f_l = sum_e E_e v_l^T KE u_l, gx, dfdx, dgdx for all cases in
+        one pass over the elements -> (fx, gx, f_case).  V_list None, or an entry None: V_l = U_l (compliance);
+        w None: all weights 1.  sums=False: nothing is reduced and the host does not wait -> (None, None, None)."""
+        n = len(U_list)
+        Ua = (C.c_void_p * max(n, 1))(*[_ptr(u) for u in U_list])
+        Va = None if V_list is None else (C.c_void_p * max(n, 1))(*[_ptr(v) for v in V_list])
+        wa = None if w is None else (C.c_double * max(n, 1))(*[float(v) for v in w])
+        fx, gx, fc = C.c_double(), C.c_double(), (C.c_double * max(n, 1))()
+        _chk(self.L.tp_elasticity_response(self.handle, n, Ua, Va, wa, _ptr(xPhys), Emin, Emax, penal, volfrac,
+                                           fc if sums else None, C.byref(fx) if sums else None, C.byref(gx) if sums else None,
+                                           _ptr(dfdx), _ptr(dgdx)), "tp_elasticity_response")
+        return (fx.value, gx.value, list(fc)[:n]) if sums else (None, None, None)
 
     def Objective(self, xPhys, Emin, Emax, penal, volfrac, dfdx=None, dgdx=None):
         fx, gx = C.c_double(), C.c_double()
@@ -383,20 +449,30 @@ class LinearElasticity:
         return fx.value, gx.value
 
     def ComputeObjectiveConstraintsSensitivities(self, dfdx, dgdx, xPhys, Emin, Emax, penal, volfrac, hist_cap=0):
-        """LinearElasticity.cc:363-445 -> (fx, gx)"""
+        """LinearElasticity.cc:363-445 -> (fx, gx); several load cases: fx = sum_l w_l u_l^T K u_l (last_f_case: the f_l)"""
         self.SolveState(xPhys, Emin, Emax, penal, hist_cap)
+        if self.ncases > 1:
+            fx, gx, self.last_f_case = self.Response(self._case_U, None, self.case_weight, xPhys, Emin, Emax, penal, volfrac,
+                                                     dfdx, dgdx)
+            return fx, gx
         return self.Objective(xPhys, Emin, Emax, penal, volfrac, dfdx, dgdx)
 
     def ComputeObjectiveConstraints(self, xPhys, Emin, Emax, penal, volfrac, hist_cap=0):
         """LinearElasticity.cc:225-297: solve, then fx and gx -- no sensitivities -> (fx, gx)"""
         self.SolveState(xPhys, Emin, Emax, penal, hist_cap)
+        if self.ncases > 1:
+            fx, gx, self.last_f_case = self.Response(self._case_U, None, self.case_weight, xPhys, Emin, Emax, penal, volfrac)
+            return fx, gx
         fx, gx = C.c_double(), C.c_double()
         _chk(self.L.tp_elasticity_objective_only(self.handle, _ptr(self.U), _ptr(xPhys), Emin, Emax, penal, volfrac,
                                                  C.byref(fx), C.byref(gx)), "tp_elasticity_objective_only")
         return fx.value, gx.value
 
     def ComputeSensitivities(self, dfdx, dgdx, xPhys, Emin, Emax, penal, volfrac=0.0):
-        """LinearElasticity.cc:299-361: dfdx, dgdx of the current state U (no solve)"""
+        """LinearElasticity.cc:299-361: dfdx, dgdx of the current state U (no solve); several load cases: of all states"""
+        if self.ncases > 1:
+            self.Response(self._case_U, None, self.case_weight, xPhys, Emin, Emax, penal, volfrac, dfdx, dgdx, sums=False)
+            return
         _chk(self.L.tp_elasticity_sensitivities(self.handle, _ptr(self.U), _ptr(xPhys), Emin, Emax, penal, _ptr(dfdx),
                                                 _ptr(dgdx) if dgdx is not None else None), "tp_elasticity_sensitivities")
 

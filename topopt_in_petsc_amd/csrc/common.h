@@ -189,6 +189,17 @@ __global__ __launch_bounds__(BLK) void k_reduce_final(const double *__restrict__
     }
 }
 
+// the same with the number of values known at run time only (tp_elasticity_response: one sum per load case + the volume)
+__global__ __launch_bounds__(BLK) void k_reduce_final_n(const double *__restrict__ partials, int nblocks, int nv,
+                                                        double *__restrict__ out) {
+    for (int v = 0; v < nv; v++) {
+        double s = 0.0;
+        for (int b = threadIdx.x; b < nblocks; b += BLK) s += partials[(long)v * nblocks + b];
+        s = block_sum(s);
+        if (threadIdx.x == 0) out[v] = s;
+    }
+}
+
 // ---------------------------------------------------------------------------
 // BLAS-1 style kernels (grid-stride, coefficients read from device scalars so
 // that the Krylov loop needs no host round trip for them)

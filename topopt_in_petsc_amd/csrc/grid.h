@@ -101,20 +101,23 @@ inline void count_launch(tp_grid *g, double bytes = 0.0, double flops = 0.0) {
     g->flops += flops;
 }
 
-// scal[slot .. slot+NV) holds this rank's sums (written by the producing kernel's reduce_tail): sum over ranks
-template <int NV>
-inline int finish_reduction(tp_grid *g, int slot) {
+// scal[slot .. slot+nv) holds this rank's sums (written by the producing kernel's reduce_tail): sum over ranks
+inline int finish_reduction_n(tp_grid *g, int slot, int nv) {
     if (g->has_comm) {
         CommMark cm(g, 2, g->stream);
         if (g->comm.allreduce_inplace) {  // the CG scalars are reduced where they live
-            if (g->comm.allreduce_inplace(g->comm.user, g->scal + slot, NV)) return TP_ERR_COMM;
+            if (g->comm.allreduce_inplace(g->comm.user, g->scal + slot, nv)) return TP_ERR_COMM;
         } else {
-            TP_HIP(hipMemcpyAsync(g->comm.red, g->scal + slot, sizeof(double) * NV, hipMemcpyDeviceToDevice, g->stream));
-            if (g->comm.allreduce_sum(g->comm.user, NV)) return TP_ERR_COMM;
-            TP_HIP(hipMemcpyAsync(g->scal + slot, g->comm.red, sizeof(double) * NV, hipMemcpyDeviceToDevice, g->stream));
+            TP_HIP(hipMemcpyAsync(g->comm.red, g->scal + slot, sizeof(double) * nv, hipMemcpyDeviceToDevice, g->stream));
+            if (g->comm.allreduce_sum(g->comm.user, nv)) return TP_ERR_COMM;
+            TP_HIP(hipMemcpyAsync(g->scal + slot, g->comm.red, sizeof(double) * nv, hipMemcpyDeviceToDevice, g->stream));
         }
     }
     return TP_OK;
+}
+template <int NV>
+inline int finish_reduction(tp_grid *g, int slot) {
+    return finish_reduction_n(g, slot, NV);
 }
 
 // The reductions finished inside the producing kernel (reduce_tail, common.h) rely on relaxed agent-scope atomics and an
@@ -142,6 +145,13 @@ inline int reduce_partials(tp_grid *g, int nblocks, int slot) {
     TP_LAUNCH(k_reduce_final<NV>, dim3(1), dim3(BLK), 0, g->stream, g->partials, nblocks, g->scal + slot);
     count_launch(g);
     return finish_reduction<NV>(g, slot);
+}
+
+// the same for a number of values known at run time, block partials [value][block] in a buffer of the caller's
+inline int reduce_partials_n(tp_grid *g, const double *partials, int nblocks, int nv, int slot) {
+    TP_LAUNCH(k_reduce_final_n, dim3(1), dim3(BLK), 0, g->stream, partials, nblocks, nv, g->scal + slot);
+    count_launch(g);
+    return finish_reduction_n(g, slot, nv);
 }
 
 // blocking read of device scalars (the only host synchronisation of the Krylov loop)

@@ -533,6 +533,8 @@ struct tp_elasticity {
     int nflagged;
     double *d_bN;            // RHS .* N scratch
     double *d_N;             // copy of N (for the load masking of :542)
+    double *d_resp = nullptr;  // block partials of tp_elasticity_response, (TP_MAX_CASES + 1) x resp_nb, allocated by its first sums
+    long resp_nb = 0;
     bool have_bc, assembled;
 };
 
@@ -693,7 +695,7 @@ extern "C" int tp_elasticity_destroy(tp_elasticity *e) {
     for (void *p : {(void *)e->d_KE, (void *)e->d_M, (void *)e->d_E, (void *)e->d_mask, (void *)e->d_bN, (void *)e->d_N,
                     (void *)e->d_flagged, (void *)e->d_colmask, (void *)e->d_flag_all, (void *)e->d_corr_nodes,
                     (void *)e->d_corr_adj, (void *)e->d_dK, (void *)e->d_corr, (void *)e->d_corr_tmp, (void *)e->d_KelF,
-                    (void *)e->d_fidx1, (void *)e->d_M2, (void *)e->d_flag2, (void *)e->d_list2})
+                    (void *)e->d_fidx1, (void *)e->d_M2, (void *)e->d_flag2, (void *)e->d_list2, (void *)e->d_resp})
         (void)hipFree(p);
     delete e;
     return TP_OK;
@@ -1304,6 +1306,142 @@ extern "C" int tp_elasticity_sensitivities(tp_elasticity *e, const double *U, co
                                            double penal, double *dfdx, double *dgdx) {
     if (!e || !U || !xPhys || !dfdx) return TP_ERR_ARG;
     return tp_elasticity_objective(e, U, xPhys, Emin, Emax, penal, 0.0, nullptr, nullptr, dfdx, dgdx);
+}
+
+// ---- several load cases: the weighted response  sum_l w_l sum_e E_e v_l^T KE u_l  and its sensitivity in one pass
+// (V_l = U_l: compliance of case l; V_l an adjoint state: the sensitivity of any linear response of U_l).
+// One thread per own element like k_objective, the cases in a loop inside the thread: xPhys is read once, pow is
+// evaluated once (x^p = x^(p-1) x), dfdx is written once.  The registers hold ONE case's u_e at a time (48 VGPRs); v_e is
+// never held -- entry r is read where row r of KE u_e is complete, and used once.  BILINEAR = false (every V_l is U_l)
+// has no loads of V at all.  REDUCE: ncase + 1 block sums (f_l = sum_e E_e v_l^T KE u_l, unweighted, and the volume) to
+// partials[value][block], same layout and summation order as k_objective's two.
+struct RespArgs {
+    const double *U[TP_MAX_CASES];
+    const double *V[TP_MAX_CASES];  // BILINEAR: never NULL (the host puts U[l] where the caller passed none)
+    double w[TP_MAX_CASES];
+    int ncase;
+};
+template <bool BILINEAR, bool REDUCE>
+__global__ __launch_bounds__(BLK) void k_response(Geom g, const double *__restrict__ KE, RespArgs a,
+                                                  const double *__restrict__ x, double Emin, double Emax, double penal,
+                                                  double *__restrict__ dfdx, double *__restrict__ partials) {
+    const long nel = g.own_elems();
+    const long t = blockIdx.x * (long)BLK + threadIdx.x;
+    const bool in = t < nel;
+    long nd0 = 0;
+    double xe = 0.0, xp1 = 0.0, E = 0.0;
+    if (in) {
+        const int i = (int)(t % g.ex), j = (int)((t / g.ex) % g.ey), k = (int)(t / ((long)g.ex * g.ey));
+        nd0 = (long)i + (long)g.nx * (j + (long)g.ny * k);
+        xe = x[t];
+        xp1 = pow(xe, penal - 1);
+        E = Emin + (xe == 0.0 ? 0.0 : xp1 * xe) * (Emax - Emin);  // (x = 0: x^p = 0 for p > 0 whatever x^(p-1) is)
+    }
+    double acc = 0.0;
+    for (int l = 0; l < a.ncase; l++) {
+        double vKu = 0.0;
+        if (in) {
+            const double *__restrict__ U = a.U[l];
+            double ue[24];
+#pragma unroll
+            for (int c8 = 0; c8 < 8; c8++) {
+                const long nd = nd0 + LXc(c8) + (long)g.nx * (LYc(c8) + (long)g.ny * LZc(c8));
+#pragma unroll
+                for (int c = 0; c < 3; c++) ue[3 * c8 + c] = U[3 * nd + c];
+            }
+            const double *__restrict__ V = BILINEAR ? a.V[l] : nullptr;
+#pragma unroll
+            for (int r = 0; r < 24; r++) {
+                double s = 0.0;
+#pragma unroll
+                for (int c = 0; c < 24; c++) s = fma(KE[r * 24 + c], ue[c], s);
+                double vr = ue[r];
+                if (BILINEAR) {
+                    const long nd = nd0 + LXc(r / 3) + (long)g.nx * (LYc(r / 3) + (long)g.ny * LZc(r / 3));
+                    vr = V[3 * nd + r % 3];
+                }
+                vKu = fma(vr, s, vKu);
+            }
+            acc = fma(a.w[l], vKu, acc);
+        }
+        if (REDUCE) {  // (every thread of the workgroup passes here: l is uniform)
+            const double f = block_sum(E * vKu);
+            if (threadIdx.x == 0) partials[(long)l * gridDim.x + blockIdx.x] = f;
+        }
+    }
+    if (in && dfdx) dfdx[t] = -1.0 * penal * xp1 * (Emax - Emin) * acc;
+    if (REDUCE) {
+        const double vol = block_sum(xe);
+        if (threadIdx.x == 0) partials[(long)a.ncase * gridDim.x + blockIdx.x] = vol;
+    }
+}
+
+extern "C" int tp_elasticity_response(tp_elasticity *e, int ncase, const double *const *U, const double *const *V, const double *w,
+                                      const double *xPhys, double Emin, double Emax, double penal, double volfrac, double *f_case,
+                                      double *fx, double *gx, double *dfdx, double *dgdx) {
+    if (!e || !U || !xPhys || ncase < 1 || ncase > TP_MAX_CASES) return TP_ERR_ARG;
+    for (int l = 0; l < ncase; l++)
+        if (!U[l]) return TP_ERR_ARG;
+    tp_grid *g = e->grid;
+    Geom q = e->mg.lv[0].g;
+    const long nel = q.own_elems();
+    const long nel_glob = (long)g->ex * g->ey * g->ez_glob;
+    RespArgs a{};
+    a.ncase = ncase;
+    bool bilinear = false;
+    const double *distinct[2 * TP_MAX_CASES];
+    int ndistinct = 0;
+    auto note = [&](const double *p) {
+        for (int i = 0; i < ndistinct; i++)
+            if (distinct[i] == p) return;
+        distinct[ndistinct++] = p;
+    };
+    for (int l = 0; l < ncase; l++) {
+        a.U[l] = U[l];
+        a.V[l] = (V && V[l]) ? V[l] : U[l];
+        a.w[l] = w ? w[l] : 1.0;
+        bilinear = bilinear || a.V[l] != a.U[l];
+        note(a.U[l]);
+        note(a.V[l]);
+    }
+    for (int i = 0; i < ndistinct; i++) TP_TRY(halo_nodes(g, q, const_cast<double *>(distinct[i]), 3));  // DMGlobalToLocal, :388-390
+    const int nb = (int)((nel + BLK - 1) / BLK);
+    const double bytes = 24.0 * q.owned_nodes() * ndistinct + 16.0 * nel, flops = 2.0 * 600 * nel * ncase;
+    if (!fx && !gx && !f_case) {  // sensitivities only: no reduction, no host synchronisation
+        if (dfdx) {
+            if (bilinear)
+                TP_LAUNCH((k_response<true, false>), dim3(nb), dim3(BLK), 0, g->stream, q, e->d_KE, a, xPhys, Emin, Emax, penal, dfdx, (double *)nullptr);
+            else
+                TP_LAUNCH((k_response<false, false>), dim3(nb), dim3(BLK), 0, g->stream, q, e->d_KE, a, xPhys, Emin, Emax, penal, dfdx, (double *)nullptr);
+            count_launch(g, bytes, flops);
+        }
+    } else {
+        if (e->resp_nb < nb) {  // (the grid's own partials hold four values per workgroup)
+            TP_HIP(hipStreamSynchronize(g->stream));
+            (void)hipFree(e->d_resp);
+            e->d_resp = nullptr;
+            e->resp_nb = 0;
+            TP_HIP(hipMalloc((void **)&e->d_resp, sizeof(double) * (TP_MAX_CASES + 1) * (size_t)nb));
+            e->resp_nb = nb;
+        }
+        if (bilinear)
+            TP_LAUNCH((k_response<true, true>), dim3(nb), dim3(BLK), 0, g->stream, q, e->d_KE, a, xPhys, Emin, Emax, penal, dfdx, e->d_resp);
+        else
+            TP_LAUNCH((k_response<false, true>), dim3(nb), dim3(BLK), 0, g->stream, q, e->d_KE, a, xPhys, Emin, Emax, penal, dfdx, e->d_resp);
+        count_launch(g, bytes, flops);
+        TP_TRY(reduce_partials_n(g, e->d_resp, nb, ncase + 1, S_TMP));
+        double v[TP_MAX_CASES + 1];
+        TP_TRY(read_scal(g, S_TMP, ncase + 1, v));
+        double f = 0.0;
+        for (int l = 0; l < ncase; l++) {
+            if (f_case) f_case[l] = v[l];
+            f = fma(a.w[l], v[l], f);
+        }
+        if (fx) *fx = f;
+        if (gx) *gx = v[ncase] / (double)nel_glob - volfrac;
+    }
+    if (dgdx) TP_TRY(tp_vec_set(g, dgdx, 1.0 / (double)nel_glob, nel));
+    return TP_OK;
 }
 
 extern "C" int tp_elasticity_set_tolerances(tp_elasticity *e, double rtol, double atol, double dtol, int max_it) {

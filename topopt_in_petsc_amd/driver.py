@@ -60,6 +60,9 @@ class TopOpt:
     mma_robust_asymptotes: int = 0
     mma_constraint_modification: bool = False
     kkt: bool = False              # MMA::KKTresidual after every Update -> kkt_norm2 / kkt_normInf in the record
+    # further load cases behind the reference's one: a list of (RHS tensor | "top", weight); the objective is the weighted
+    # sum of the cases' compliances on the shared supports (None: the reference's single case, nothing changes)
+    loadcases: list = None
     history: list = field(default_factory=list)
 
     def __post_init__(self):
@@ -70,6 +73,13 @@ class TopOpt:
         so = self.solver or SolverOptions(nlvls=self.nlvls, nu=self.nu)
         self.physics = LinearElasticity(self.grid, so)
         self.physics.SetUpLoadAndBC()
+        for rhs, weight in (self.loadcases or ()):
+            if isinstance(rhs, str):
+                if rhs != "top":
+                    raise ValueError("unknown load case %r (the only name is 'top')" % (rhs,))
+                self.physics.SetUpLoadAndBC_Top(weight)
+            else:
+                self.physics.AddLoadCase(rhs, weight)
         self.filt = Filter(self.grid, self.filter, self.rmin)
         g = self.grid
         # TopOpt.cc:362-381: all design fields start at volfrac
@@ -130,6 +140,10 @@ class TopOpt:
                    mma_inner=self.mma.last_inner)
         if self.kkt:
             rec["kkt_norm2"], rec["kkt_normInf"] = kkt
+        if self.physics.ncases > 1:   # ksp_its: the sum over the cases; ksp_rerr: the last case's
+            rec["f_case"] = list(self.physics.last_f_case)
+            rec["ksp_its_case"] = list(self.physics.case_its)
+            rec["ksp_its"] = sum(self.physics.case_its)
         self.history.append(rec)
         if verbose and self.rank == 0:
             print("It.: %i, True fx: %f, Scaled fx: %f, gx[0]: %f, ch.: %f, mnd.: %f, time: %f"
@@ -160,11 +174,12 @@ class TopOpt:
         xo1, xo2, U, L = g.elem_vec(), g.elem_vec(), g.elem_vec(), g.elem_vec()
         self.mma.Restart(xo1, xo2, U, L)
         vecs = [self._gather(v) for v in (self.x, self.xPhys, xo1, xo2, U, L)]
-        sol = self._gather(self.physics.U[self.grid.part.owned_slice(3)])
+        # the further cases' states follow the first Vec (the reference's reader takes the first one only)
+        sols = [self._gather(self.physics.LoadCaseU(c)[self.grid.part.owned_slice(3)]) for c in range(self.physics.ncases)]
         prefix = os.path.join(self.workdir, "Restart" + tag)
         if self.rank == 0:
             mpiio.write_restart(prefix, self.itr, self.fscale, *vecs)
-            mpiio.write_petsc_vecs(os.path.join(self.workdir, "RestartSol%s.dat" % tag), [sol])
+            mpiio.write_petsc_vecs(os.path.join(self.workdir, "RestartSol%s.dat" % tag), sols)
         return prefix
 
     def ReadRestartFiles(self, vecfile, itrfile, solfile=None):
@@ -178,11 +193,13 @@ class TopOpt:
         if not self.onlyLoadDesign:
             self.mma.SetRestart(self.itr, self._own(xo1), self._own(xo2), self._own(U), self._own(L))
         if solfile and os.path.exists(solfile):
-            sol, = mpiio.read_petsc_vecs(solfile)
-            self.physics.U.zero_()
+            sols = mpiio.read_petsc_vecs(solfile)   # a file with fewer states than cases leaves the others at zero
             sl = self.grid.part.owned_slice(3)
             n0 = 3 * self.grid.part.plane * (self.grid.part.node_z0 + self.grid.part.own_lo)
-            self.physics.U[sl] = torch.from_numpy(sol[n0:n0 + (sl.stop - sl.start)].copy()).to(self.x.device)
+            for c, sol in enumerate(sols[:self.physics.ncases]):
+                U = self.physics.LoadCaseU(c)
+                U.zero_()
+                U[sl] = torch.from_numpy(sol[n0:n0 + (sl.stop - sl.start)].copy()).to(self.x.device)
 
     def WriteVTK(self, itr):
         if self._out is not None:

@@ -103,6 +103,8 @@ SYMBOLS = {
     "tp_elasticity_objective": (_i, [_vp, _vp, _vp, _d, _d, _d, _d, C.POINTER(_d), C.POINTER(_d), _vp, _vp]),
     "tp_elasticity_objective_only": (_i, [_vp, _vp, _vp, _d, _d, _d, _d, C.POINTER(_d), C.POINTER(_d)]),
     "tp_elasticity_sensitivities": (_i, [_vp, _vp, _vp, _d, _d, _d, _vp, _vp]),
+    "tp_elasticity_response": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_d), _vp, _d, _d, _d, _d, C.POINTER(_d),
+                                    C.POINTER(_d), C.POINTER(_d), _vp, _vp]),
     "tp_elasticity_petsc_options": (_i, [_vp, C.c_char_p, C.c_size_t]),
     "tp_elasticity_level_count": (_i, [_vp]),
     "tp_elasticity_level_nodes": (_l, [_vp, _i]),
@@ -160,6 +162,7 @@ SYMBOLS = {
 
 
 ABI_VERSION = 4   # TP_ABI_VERSION of include/topopt_amd.h
+MAX_CASES = 8     # TP_MAX_CASES: load cases of one tp_elasticity_response call
 
 
 def load_library():
