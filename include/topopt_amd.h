@@ -276,6 +276,25 @@ int tp_elasticity_response(tp_elasticity *e, int ncase,
         double *fx, double *gx,   /* fx = sum_l w_l f_l ; gx as tp_elasticity_objective; may be NULL    */
         double *dfdx,             /* [dev] -p x^(p-1) (Emax-Emin) sum_l w_l v_l^T KE u_l ; may be NULL  */
         double *dgdx);            /* [dev] 1/n ; may be NULL                                            */
+/* Relaxed von Mises stress at the element centroids, its p-norm over all ranks, and the two ingredients of the
+ * p-norm's design sensitivity.  U [dev, local nodes*3] (ghost planes refreshed inside); xPhys [dev, own elements].
+ * With B0 the strain-displacement matrix at the centroid, C the unit-modulus isotropic matrix and Vm the von Mises matrix,
+ * M = B0^T C^T Vm C B0 (tp_elasticity_get_stress_form; always from the grid's h and opts.nu, also with a caller's KE):
+ *   s_e = u_e^T M u_e,  vm_e = Emax x_e^q sqrt(s_e),  pnorm = (sum_e vm_e^P)^(1/P)
+ *   dpdx_e  = pnorm^(1-P) q Emax^P x_e^(qP-1) s_e^(P/2)                        (explicit part, 0 at x_e = 0)
+ *   adj_rhs = d pnorm / dU = sum_e pnorm^(1-P) (Emax x_e^q)^P s_e^((P-2)/2) L_e^T M u_e   (owned planes; N NOT applied)
+ * Total derivative: solve K lambda = N adj_rhs (tp_elasticity_solve applies N), then
+ *   d pnorm / dx = dpdx + dfdx of tp_elasticity_response(ncase 1, U = u, V = lambda, w = NULL), no sums.
+ * Elements with s_e = 0 contribute exactly 0; pnorm = 0 leaves dpdx and adj_rhs all zero.  With only vm asked for
+ * nothing is reduced and the host does not wait; otherwise one reduction and one host read.
+ * TP_ERR_ARG unless P >= 2, q >= 0 and (q == 0 or q P >= 1). */
+int tp_elasticity_stress(tp_elasticity *e, const double *U, const double *xPhys, double Emax, double q, double P,
+        double *vm,       /* [dev, own elements]; may be NULL */
+        double *pnorm,    /* host; may be NULL */
+        double *vm_max,   /* host, max over all ranks; may be NULL */
+        double *dpdx,     /* [dev, own elements] explicit part; may be NULL */
+        double *adj_rhs); /* [dev, local nodes*3] d pnorm / dU on owned planes; may be NULL */
+int tp_elasticity_get_stress_form(const tp_elasticity *e, double *m_host_576);
 /* introspection for parity tests */
 /* KSPSetTolerances (LinearElasticity.cc:646); a negative value keeps the current one (PETSC_DEFAULT) */
 int tp_elasticity_set_tolerances(tp_elasticity *le, double rtol, double atol, double dtol, int max_it);

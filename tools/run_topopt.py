@@ -1,8 +1,9 @@
 #!/usr/bin/env python
 """End-to-end run of the reference's optimisation loop on the MI355X path.
-usage: run_topopt.py [--loadcase top[:weight]]... ex ey ez nlvls n_iter [filter [nsmooth ncoarse]]
+usage: run_topopt.py [--loadcase top[:weight]]... [--stress-limit L [--stress-p P] [--stress-q q]] ex ey ez nlvls n_iter [filter [nsmooth ncoarse]]
 (e.g. 128 128 128 5 20 1 2 45: the cycle of bench.py; --loadcase top:0.5 adds the line load on the upper edge as a second load
-case of weight 0.5 -- the objective becomes the weighted sum of the cases' compliances)"""
+case of weight 0.5 -- the objective becomes the weighted sum of the cases' compliances; --stress-limit L holds the von Mises
+p-norm of load case 0 below L as a second constraint, exponent --stress-p (8), stress relaxation x^q with --stress-q (0.5))"""
 import os
 import sys
 
@@ -31,12 +32,34 @@ def _loadcases(argv):
     return cases, rest
 
 
+def _number_option(argv, name):
+    """takes `name value` / `name=value` out of argv -> (float | None, the rest)"""
+    val, rest, i = None, [], 0
+    while i < len(argv):
+        a = argv[i]
+        if a == name or a.startswith(name + "="):
+            if a == name:
+                i += 1
+                if i >= len(argv):
+                    sys.exit("%s needs a value" % name)
+            val = float(argv[i] if a == name else a.split("=", 1)[1])
+        else:
+            rest.append(a)
+        i += 1
+    return val, rest
+
+
 loadcases, sys.argv[1:] = _loadcases(sys.argv[1:])
+stress_limit, sys.argv[1:] = _number_option(sys.argv[1:], "--stress-limit")
+stress_p, sys.argv[1:] = _number_option(sys.argv[1:], "--stress-p")
+stress_q, sys.argv[1:] = _number_option(sys.argv[1:], "--stress-q")
+stress = {} if stress_limit is None else dict(stress_limit=stress_limit, stress_P=8.0 if stress_p is None else stress_p,
+                                              stress_q=0.5 if stress_q is None else stress_q)
 ex, ey, ez, nlv, nit = [int(v) for v in sys.argv[1:6]]
 flt = int(sys.argv[6]) if len(sys.argv) > 6 else 1
 h = 1.0 / ey
 opt = tp.TopOpt(nxyz=(ex + 1, ey + 1, ez + 1), xc=(0, ex * h, 0, 1, 0, ez * h), nlvls=nlv, rmin=2.56 * h, filter=flt,
-                loadcases=loadcases or None,
+                loadcases=loadcases or None, **stress,
                 solver=tp.SolverOptions(nlvls=nlv, **(dict(nsmooth=int(sys.argv[7]), ncoarse=int(sys.argv[8])) if len(sys.argv) > 8 else {})))
 print("# %dx%dx%d elements, %d DOF, %d MG levels, filter %d, rmin %.4f" % (ex, ey, ez, 3 * (ex + 1) * (ey + 1) * (ez + 1), nlv, flt, 2.56 * h))
 for it in range(nit):
@@ -44,3 +67,6 @@ for it in range(nit):
     print("State solver:  iter: %i, rerr.: %e | MMA inner its: %d" % (r["ksp_its"], r["ksp_rerr"], r["mma_inner"]), flush=True)
     if "f_case" in r:
         print("Load cases:    f: %s | iter: %s" % (" ".join("%e" % f for f in r["f_case"]), " ".join("%d" % k for k in r["ksp_its_case"])), flush=True)
+    if "stress_pnorm" in r:
+        print("Stress:        p-norm: %e, max: %e, gx[1]: %f | adjoint iter: %d"
+              % (r["stress_pnorm"], r["stress_max"], r["gx_stress"], r["ksp_its_adjoint"]), flush=True)

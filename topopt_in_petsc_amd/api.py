@@ -279,6 +279,9 @@ class LinearElasticity:
         self._case_rhs, self._case_U, self.case_weight = [self.RHS], [self.U], [1.0]
         self.case_its, self.case_rnorm, self.case_bnorm = [0], [0.0], [0.0]
         self.last_f_case = None
+        # stress constraint: the adjoint state persists like the states (warm start); allocated by the first StressSensitivity
+        self.lam = self._stress_dpdx = self._stress_rhs = None
+        self.adjoint_its, self.adjoint_rnorm, self.adjoint_bnorm = 0, 0.0, 0.0
 
     def close(self):
         if getattr(self, "handle", None):
@@ -440,6 +443,49 @@ class LinearElasticity:
                                            fc if sums else None, C.byref(fx) if sums else None, C.byref(gx) if sums else None,
                                            _ptr(dfdx), _ptr(dgdx)), "tp_elasticity_response")
         return (fx.value, gx.value, list(fc)[:n]) if sums else (None, None, None)
+
+    def StressForm(self):
+        """the von Mises form M = B0^T C^T Vm C B0 of the element (24 x 24 row-major, numpy array of 576): s_e = u_e^T M u_e"""
+        import numpy as np
+        m = np.zeros(576)
+        _chk(self.L.tp_elasticity_get_stress_form(self.handle, m.ctypes.data), "tp_elasticity_get_stress_form")
+        return m
+
+    def Stress(self, xPhys, Emax, q, P, U=None, vm=None, dpdx=None, adj_rhs=None):
+        """tp_elasticity_stress on the state U (default: case 0's): vm_e = Emax x_e^q sqrt(u_e^T M u_e) into vm, the explicit
+        part of d pnorm / dx into dpdx, d pnorm / dU (owned planes, supports not applied) into adj_rhs -> (pnorm, vm_max).
+        With vm the only output nothing is reduced, the host does not wait and (None, None) comes back (the field together with
+        the two numbers: ask for dpdx as well)."""
+        sums = not (vm is not None and dpdx is None and adj_rhs is None)
+        pn, mx = C.c_double(), C.c_double()
+        _chk(self.L.tp_elasticity_stress(self.handle, _ptr(self.U if U is None else U), _ptr(xPhys), Emax, q, P, _ptr(vm),
+                                         C.byref(pn) if sums else None, C.byref(mx) if sums else None, _ptr(dpdx), _ptr(adj_rhs)),
+             "tp_elasticity_stress")
+        return (pn.value, mx.value) if sums else (None, None)
+
+    def StressSensitivity(self, dsdx, xPhys, Emin, Emax, penal, q, P, case=0):
+        """d pnorm / dx of the von Mises p-norm of load case `case` on the CURRENT assembly and state -> (pnorm, vm_max, its):
+        Stress, the adjoint solve K lam = N adj_rhs (warm-started from the previous design iteration's lam), the bilinear
+        pass of Response with V = lam, and dsdx += dpdx.  The adjoint solve's figures go to adjoint_its / adjoint_rnorm /
+        adjoint_bnorm; last_its and the per-case records of the state solves stay as they are."""
+        if self.lam is None:
+            self.lam, self._stress_rhs = self.grid.node_vec(3), self.grid.node_vec(3)   # (ghost planes of the load stay 0)
+            self._stress_dpdx = self.grid.elem_vec()
+        U = self._case_U[case]
+        pn, mx = self.Stress(xPhys, Emax, q, P, U=U, dpdx=self._stress_dpdx, adj_rhs=self._stress_rhs)
+        its, rn, bn = C.c_int(), C.c_double(), C.c_double()
+        if pn == 0.0:   # no stress anywhere: a zero load, whose solution is lam = 0 -- no solve
+            self.lam.zero_()
+            self.adjoint_its, self.adjoint_rnorm, self.adjoint_bnorm = 0, 0.0, 0.0
+            dsdx.zero_()
+            return pn, mx, 0
+        rc = self.L.tp_elasticity_solve(self.handle, _ptr(self._stress_rhs), _ptr(self.lam), C.byref(its), C.byref(rn),
+                                        C.byref(bn), None, 0)
+        self.adjoint_its, self.adjoint_rnorm, self.adjoint_bnorm = its.value, rn.value, bn.value
+        _chk(rc, "tp_elasticity_solve (adjoint)")
+        self.Response([U], [self.lam], None, xPhys, Emin, Emax, penal, 0.0, dfdx=dsdx, sums=False)
+        _chk(self.L.tp_vec_axpby(self.grid.handle, _ptr(dsdx), 1.0, _ptr(self._stress_dpdx), 1.0, dsdx.numel()), "tp_vec_axpby")
+        return pn, mx, its.value
 
     def Objective(self, xPhys, Emin, Emax, penal, volfrac, dfdx=None, dgdx=None):
         fx, gx = C.c_double(), C.c_double()

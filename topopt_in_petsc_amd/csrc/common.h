@@ -109,6 +109,27 @@ __device__ inline double block_sum(double v) {
     return t;
 }
 
+// the same for the maximum: block maximum in thread 0 (BLK threads); fmax is exact, any order gives the same bits
+__device__ inline double wave_max(double v) {
+#pragma unroll
+    for (int off = WAVE / 2; off > 0; off >>= 1) v = fmax(v, __shfl_down(v, off, WAVE));
+    return v;
+}
+__device__ inline double block_max(double v) {
+    __shared__ double s_mpart[BLK / WAVE];
+    v = wave_max(v);
+    const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
+    __syncthreads();  // protect s_mpart reuse across consecutive calls
+    if (lane == 0) s_mpart[w] = v;
+    __syncthreads();
+    double t = v;
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int i = 1; i < BLK / WAVE; i++) t = fmax(t, s_mpart[i]);
+    }
+    return t;
+}
+
 // Tail of a reducing kernel: every workgroup has its NV partial sums in thread 0 (block_sum); they are written to
 // partials[v * nb + b] and the LAST workgroup to arrive adds them up in the same fixed order as k_reduce_final --
 // bitwise the same result, one launch less per dot product.  Hand-off per MI355X_MICROARCH.md ("8-byte agent atomics

@@ -78,6 +78,53 @@ inline void hex8_stiffness_box(double dx, double dy, double dz, double nu, doubl
             }
 }
 
+// Von Mises form of the box element at its centroid: M = B0^T C^T Vm C B0 with B0 the 6 x 24 strain-displacement matrix
+// at xi = eta = zeta = 0 (node order and strain rows xx, yy, zz, xy, yz, zx of hex8_stiffness_box, engineering shear),
+// C the unit-modulus isotropic matrix built there and Vm the von Mises matrix (1 on the normal diagonal, -1/2 between
+// normals, 3 on the shear diagonal):  u_e^T M u_e = sigma_vm^2 of the unit-modulus stress C B0 u_e.  Symmetric by
+// construction (the two triangles are computed as one value); M annihilates rigid translations to rounding.
+inline void hex8_vonmises_form_box(double dx, double dy, double dz, double nu, double *M /*576*/) {
+    const double sg[3][8] = {{-1, 1, 1, -1, -1, 1, 1, -1}, {-1, -1, 1, 1, -1, -1, 1, 1}, {-1, -1, -1, -1, 1, 1, 1, 1}};
+    const double hd[3] = {dx, dy, dz};
+    const double lambda = nu / ((1.0 + nu) * (1.0 - 2.0 * nu)), mu = 1.0 / (2.0 * (1.0 + nu));
+    double C[6][6] = {}, Vm[6][6] = {};
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++) {
+            C[i][j] = lambda;
+            Vm[i][j] = -0.5;
+        }
+        C[i][i] = lambda + 2.0 * mu;
+        C[i + 3][i + 3] = mu;
+        Vm[i][i] = 1.0;
+        Vm[i + 3][i + 3] = 3.0;
+    }
+    const int sel[3][6] = {{0, -1, -1, 1, -1, 2}, {-1, 1, -1, 0, 2, -1}, {-1, -1, 2, -1, 1, 0}};
+    double B[6][24] = {};
+    for (int d = 0; d < 3; d++)
+        for (int row = 0; row < 6; row++)
+            if (sel[d][row] >= 0)
+                for (int n = 0; n < 8; n++) B[row][3 * n + sel[d][row]] = sg[d][n] / (4.0 * hd[d]);  // dN_n/dx_d at the centroid
+    double S[6][24], W[6][24];  // S = C B0, W = Vm S
+    for (int i = 0; i < 6; i++)
+        for (int j = 0; j < 24; j++) {
+            double s = 0.0;
+            for (int k = 0; k < 6; k++) s += C[i][k] * B[k][j];
+            S[i][j] = s;
+        }
+    for (int i = 0; i < 6; i++)
+        for (int j = 0; j < 24; j++) {
+            double s = 0.0;
+            for (int k = 0; k < 6; k++) s += Vm[i][k] * S[k][j];
+            W[i][j] = s;
+        }
+    for (int i = 0; i < 24; i++)
+        for (int j = i; j < 24; j++) {
+            double s = 0.0;
+            for (int k = 0; k < 6; k++) s += S[k][i] * W[k][j];
+            M[24 * i + j] = M[24 * j + i] = s;
+        }
+}
+
 // Helmholtz filter element matrix KF = R^2 int grad N . grad N + int N N on a
 // box element, closed form (PDEFilter.cc:472-565); entries depend only on
 // which axes the two nodes differ along.

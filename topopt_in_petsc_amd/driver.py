@@ -63,9 +63,19 @@ class TopOpt:
     # further load cases behind the reference's one: a list of (RHS tensor | "top", weight); the objective is the weighted
     # sum of the cases' compliances on the shared supports (None: the reference's single case, nothing changes)
     loadcases: list = None
+    # stress constraint: the von Mises p-norm (exponent stress_P, stress relaxation x^stress_q) of load case stress_case held
+    # below stress_limit as a second MMA constraint g1 = pnorm / stress_limit - 1 (None: none, nothing changes)
+    stress_limit: float = None
+    stress_P: float = 8.0
+    stress_q: float = 0.5
+    stress_case: int = 0
     history: list = field(default_factory=list)
 
     def __post_init__(self):
+        if self.stress_limit is not None:
+            if not self.stress_limit > 0.0:
+                raise ValueError("stress_limit must be positive")
+            self.m = max(self.m, 2)
         nx, ny, nz = self.nxyz
         h = ((self.xc[1] - self.xc[0]) / (nx - 1), (self.xc[3] - self.xc[2]) / (ny - 1),
              (self.xc[5] - self.xc[4]) / (nz - 1))
@@ -123,11 +133,17 @@ class TopOpt:
             self.fscale = 10.0 / fx                                                              # :68-70
         fxs = fx * self.fscale
         self.dfdx.mul_(self.fscale)                                                              # :73
+        gxs = [gx]
+        if self.stress_limit is not None:   # second constraint on the assembly and state of the solve above
+            pnorm, vm_max, its_adj = self.physics.StressSensitivity(self.dgdx[1], self.xPhys, self.Emin, self.Emax, self.penal,
+                                                                    self.stress_q, self.stress_P, self.stress_case)
+            self.dgdx[1].div_(self.stress_limit)
+            gxs.append(pnorm / self.stress_limit - 1.0)
         self.filt.Gradients(self.x, self.xTilde, self.dfdx, self.dgdx, self.projectionFilter, self.beta, self.eta)
         self.mma.SetOuterMovelimit(self.Xmin, self.Xmax, self.movlim, self.x, self.xmin, self.xmax)  # :81
-        self.mma.Update(self.x, self.dfdx, [gx], self.dgdx, self.xmin, self.xmax)                # :85
+        self.mma.Update(self.x, self.dfdx, gxs, self.dgdx, self.xmin, self.xmax)                 # :85
         if self.kkt:
-            kkt = self.mma.KKTresidual(self.x, self.dfdx, [gx], self.dgdx, self.xmin, self.xmax)
+            kkt = self.mma.KKTresidual(self.x, self.dfdx, gxs, self.dgdx, self.xmin, self.xmax)
         ch = self.mma.DesignChange(self.x, self.xold)                                            # :89
         if self.projectionFilter:                                                                # :93-95
             self._increase_beta(gx, ch)
@@ -144,6 +160,8 @@ class TopOpt:
             rec["f_case"] = list(self.physics.last_f_case)
             rec["ksp_its_case"] = list(self.physics.case_its)
             rec["ksp_its"] = sum(self.physics.case_its)
+        if self.stress_limit is not None:
+            rec["stress_pnorm"], rec["stress_max"], rec["gx_stress"], rec["ksp_its_adjoint"] = pnorm, vm_max, gxs[1], its_adj
         self.history.append(rec)
         if verbose and self.rank == 0:
             print("It.: %i, True fx: %f, Scaled fx: %f, gx[0]: %f, ch.: %f, mnd.: %f, time: %f"
