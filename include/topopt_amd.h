@@ -373,6 +373,34 @@ int tp_pdefilter_solve(tp_filter *f, const double *rhs_nodal, double *u_nodal);
 int tp_pdefilter_node_to_elem(tp_filter *f, const double *u_nodal, double *x_elem);
 int tp_pdefilter_apply(tp_filter *f, const double *u_nodal, double *y_nodal);
 
+/* ---- local volume constraint (no reference counterpart; Wu, Aage, Westermann, Sigmund 2018) ---- */
+/* The mean density in a ball of radius R around every element, held below alpha through ONE p-norm constraint:
+ *   N_e = { j : |c_j - c_e| < R } over element centres (strict; truncated at the domain boundary, as the cone filter),
+ *   cnt_e = |N_e|,  rhobar_e = (sum_{j in N_e} xPhys_j) / cnt_e,
+ *   pn = ((sum_e rhobar_e^p) / n)^(1/p) over all ranks (n = global element count),  g = pn / alpha - 1,
+ *   dgdx_j = sum_{e in N_j} t_e^(p-1) / (alpha n cnt_e),  t_e = rhobar_e / pn        (pn = 0: dgdx = 0).
+ * A handle of its own on a grid (any filter type beside it, R unrelated to rmin).  The ball sums are the cone filter's
+ * convolution kernels on a 0/1 table; on more than one rank TP_ERR_ARG if the stencil is wider than a slab.  All arrays
+ * [dev, own elements].  The sum over the elements runs layer by layer in ascending global z: the results do not depend on
+ * the number of slabs, and two calls give the same bits. */
+typedef struct tp_localvol tp_localvol;
+int tp_localvol_create(tp_localvol **lv, tp_grid *g, double R);   /* TP_ERR_ARG unless R > 0 */
+int tp_localvol_destroy(tp_localvol *lv);
+int tp_localvol_stencil_width(const tp_localvol *lv);             /* max over the axes of ceil(R/h) - 1, clamped to half the mesh */
+int tp_localvol_get_count(tp_localvol *lv, double *cnt);          /* cnt_e */
+/* kernel of the last ball sum: the codes of tp_filter_last_kernel */
+int tp_localvol_last_kernel(const tp_localvol *lv);
+/* rhobar alone: one ball sum, no reduction, the host does not wait */
+int tp_localvol_mean(tp_localvol *lv, const double *xPhys, double *rhobar);
+/* TP_ERR_ARG unless p >= 1 and alpha > 0.  Without dgdx: one ball sum, one reduction, one host read (one rank); with it
+ * a coefficient pass and a second ball sum follow, no further read. */
+int tp_localvol_constraint(tp_localvol *lv, const double *xPhys, double alpha, double p,
+        double *g,          /* host; may be NULL */
+        double *pn,         /* host; may be NULL */
+        double *rhobar_max, /* host, max over all ranks; may be NULL */
+        double *rhobar,     /* [dev, own elements]; may be NULL */
+        double *dgdx);      /* [dev, own elements]; may be NULL */
+
 /* ---- MMA optimizer step on the device (MMA.cc) ------------ */
 typedef struct tp_mma tp_mma;
 /* MMA::MMA(n, m, x) (MMA.cc:108-190): a = 0, c = 1000, d = 0, asymptote factors 0.5 / 0.7 / 1.2.

@@ -1,9 +1,11 @@
 #!/usr/bin/env python
 """End-to-end run of the reference's optimisation loop on the MI355X path.
-usage: run_topopt.py [--loadcase top[:weight]]... [--stress-limit L [--stress-p P] [--stress-q q]] ex ey ez nlvls n_iter [filter [nsmooth ncoarse]]
+usage: run_topopt.py [--loadcase top[:weight]]... [--stress-limit L [--stress-p P] [--stress-q q]] [--local-volume ALPHA:R] ex ey ez nlvls n_iter [filter [nsmooth ncoarse]]
 (e.g. 128 128 128 5 20 1 2 45: the cycle of bench.py; --loadcase top:0.5 adds the line load on the upper edge as a second load
 case of weight 0.5 -- the objective becomes the weighted sum of the cases' compliances; --stress-limit L holds the von Mises
-p-norm of load case 0 below L as a second constraint, exponent --stress-p (8), stress relaxation x^q with --stress-q (0.5))"""
+p-norm of load case 0 below L as a second constraint, exponent --stress-p (8), stress relaxation x^q with --stress-q (0.5); --local-volume ALPHA:R holds the mean density in a ball of
+radius R (a length, the element size is 1/ey) around every element below ALPHA through one p-norm constraint, exponent 16, as
+the last constraint)"""
 import os
 import sys
 
@@ -55,11 +57,35 @@ stress_p, sys.argv[1:] = _number_option(sys.argv[1:], "--stress-p")
 stress_q, sys.argv[1:] = _number_option(sys.argv[1:], "--stress-q")
 stress = {} if stress_limit is None else dict(stress_limit=stress_limit, stress_P=8.0 if stress_p is None else stress_p,
                                               stress_q=0.5 if stress_q is None else stress_q)
+def _text_option(argv, name):
+    """takes `name value` / `name=value` out of argv -> (str | None, the rest)"""
+    val, rest, i = None, [], 0
+    while i < len(argv):
+        a = argv[i]
+        if a == name or a.startswith(name + "="):
+            if a == name:
+                i += 1
+                if i >= len(argv):
+                    sys.exit("%s needs a value" % name)
+            val = argv[i] if a == name else a.split("=", 1)[1]
+        else:
+            rest.append(a)
+        i += 1
+    return val, rest
+
+
+local_volume, sys.argv[1:] = _text_option(sys.argv[1:], "--local-volume")
+local = {}
+if local_volume is not None:
+    alpha, sep, radius = local_volume.partition(":")
+    if not sep:
+        sys.exit("--local-volume needs ALPHA:R, got %r" % local_volume)
+    local = dict(local_volume=float(alpha), local_volume_R=float(radius))
 ex, ey, ez, nlv, nit = [int(v) for v in sys.argv[1:6]]
 flt = int(sys.argv[6]) if len(sys.argv) > 6 else 1
 h = 1.0 / ey
 opt = tp.TopOpt(nxyz=(ex + 1, ey + 1, ez + 1), xc=(0, ex * h, 0, 1, 0, ez * h), nlvls=nlv, rmin=2.56 * h, filter=flt,
-                loadcases=loadcases or None, **stress,
+                loadcases=loadcases or None, **stress, **local,
                 solver=tp.SolverOptions(nlvls=nlv, **(dict(nsmooth=int(sys.argv[7]), ncoarse=int(sys.argv[8])) if len(sys.argv) > 8 else {})))
 print("# %dx%dx%d elements, %d DOF, %d MG levels, filter %d, rmin %.4f" % (ex, ey, ez, 3 * (ex + 1) * (ey + 1) * (ez + 1), nlv, flt, 2.56 * h))
 for it in range(nit):
@@ -70,3 +96,5 @@ for it in range(nit):
     if "stress_pnorm" in r:
         print("Stress:        p-norm: %e, max: %e, gx[1]: %f | adjoint iter: %d"
               % (r["stress_pnorm"], r["stress_max"], r["gx_stress"], r["ksp_its_adjoint"]), flush=True)
+    if "gx_local" in r:
+        print("Local volume:  p-norm: %f, max: %f, gx[%d]: %f" % (r["local_pnorm"], r["local_max"], opt.m - 1, r["gx_local"]), flush=True)

@@ -691,6 +691,54 @@ class Filter:
         return its.value, rn.value
 
 
+class LocalVolume:
+    """Local volume constraint (tp_localvol): the mean density in a ball of radius R around every element, its p-norm
+    held below alpha as one constraint g = pn / alpha - 1.  Independent of the Filter and of rmin."""
+
+    def __init__(self, grid, R):
+        self.grid, self.L = grid, grid.L
+        self.handle = C.c_void_p()
+        _chk(self.L.tp_localvol_create(C.byref(self.handle), grid.handle, float(R)), "tp_localvol_create")
+        grid._adopt(self)
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.L.tp_localvol_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def stencil_width(self):
+        return self.L.tp_localvol_stencil_width(self.handle)
+
+    def last_kernel(self):
+        """kernel of the last ball sum, the codes of Filter.last_kernel"""
+        return self.L.tp_localvol_last_kernel(self.handle)
+
+    def count(self):
+        """elements in every own element's ball (truncated at the domain boundary)"""
+        cnt = self.grid.elem_vec()
+        _chk(self.L.tp_localvol_get_count(self.handle, _ptr(cnt)), "tp_localvol_get_count")
+        return cnt
+
+    def Mean(self, xPhys, out):
+        """out = ball mean of xPhys; nothing is reduced and the host does not wait"""
+        _chk(self.L.tp_localvol_mean(self.handle, _ptr(xPhys), _ptr(out)), "tp_localvol_mean")
+        return out
+
+    def Constraint(self, xPhys, alpha, p=16.0, dgdx=None, rhobar=None):
+        """(g, pn, rhobar_max) with g = pn / alpha - 1; dgdx receives dg/dxPhys, rhobar the ball means, where given"""
+        g, pn, mx = C.c_double(), C.c_double(), C.c_double()
+        _chk(self.L.tp_localvol_constraint(self.handle, _ptr(xPhys), alpha, p, C.byref(g), C.byref(pn), C.byref(mx),
+                                           _ptr(rhobar), _ptr(dgdx)), "tp_localvol_constraint")
+        return g.value, pn.value, mx.value
+
+
 class MMA:
     """MMA (MMA.h:29-140) on the device: the design vectors stay in HBM."""
 

@@ -361,7 +361,17 @@ struct tp_filter {
     int last_kernel = 0;  // cone filter kernel of the last convolution (tp_filter_last_kernel): 1 tiled, 2 several outputs along z, 3 wide, 4 streamed ring, 5 generic
 };
 
-static int filter_conv(tp_filter *f, double *out, const double *d1, const double *d2) {
+// The convolution itself knows nothing of tp_filter: any (2c+1)^3 weight table over a ghosted copy of an element field
+// (the cone filter's here, the ball indicator of localvol.h) goes through the same dispatch and launch accounting.
+struct ConvArgs {
+    tp_grid *grid;
+    int conn;
+    const double *wtab;
+    double *xg;        // ghosted input: conn layers below, the own ones, conn above
+    long nel, lay;
+    int *last_kernel;  // receives the code of the kernel launched (tp_filter_last_kernel)
+};
+static int conv_apply(const ConvArgs *f, double *out, const double *d1, const double *d2) {
     tp_grid *g = f->grid;
     const int c = f->conn;
     // ghost layers: own first c layers -> lower neighbour's top ghosts, own last c -> upper's bottom ghosts
@@ -373,13 +383,13 @@ static int filter_conv(tp_filter *f, double *out, const double *d1, const double
     do {  \
     TP_LAUNCH(k_conv_filter_tiled<CC>, tg, dim3(256), 0, g->stream, g->ex, g->ey, g->ez_own, g->rank * g->ez_own, \
                        g->ez_glob, f->xg, f->wtab, out, d1, d2);                                                         \
-    f->last_kernel = 1;  \
+    *f->last_kernel = 1;  \
     } while (0)
 #define TP_CONV_WIDE(CC, TYE, TZE)                                                                                                   \
     do {  \
     TP_LAUNCH((k_conv_filter_wide<CC, TYE, TZE>), dim3((g->ex + 31) / 32, (g->ey + TYE - 1) / TYE, (g->ez_own + TZE - 1) / TZE), \
               dim3(8 * TYE * TZE), 0, g->stream, g->ex, g->ey, g->ez_own, g->rank * g->ez_own, g->ez_glob, f->xg, f->wtab, out, d1, d2); \
-    f->last_kernel = 3;  \
+    *f->last_kernel = 3;  \
     } while (0)
     // Round 6 (counters: the one-output form is LDS-issue bound, one ds_read per fma): the four-outputs-per-thread form was
     // measured for the small radii too, bit-equal -- ElemConn 3 (343 taps): 105.5 -> 69.8 us at 128^3, taken; ElemConn 2 (125
@@ -396,7 +406,7 @@ static int filter_conv(tp_filter *f, double *out, const double *d1, const double
     do {  \
     TP_LAUNCH((k_conv_filter_zmulti<CC, NO>), dim3((g->ex + 31) / 32, (g->ey + 3) / 4, (g->ez_own + 2 * NO - 1) / (2 * NO)), dim3(256), 0, \
               g->stream, g->ex, g->ey, g->ez_own, g->rank * g->ez_own, g->ez_glob, f->xg, f->wtab, out, d1, d2);                 \
-    f->last_kernel = 2;  \
+    *f->last_kernel = 2;  \
     } while (0)
     if (!no_tile && c == 2 && zm == 4)
         TP_CONV_ZMULTI(2, 4);
@@ -426,7 +436,7 @@ static int filter_conv(tp_filter *f, double *out, const double *d1, const double
     do {  \
     TP_LAUNCH((k_conv_filter_zring<CC>), dim3((g->ex + 31) / 32, (g->ey + 15) / 16, (g->ez_own + 3) / 4), dim3(256), 0, g->stream, \
               g->ex, g->ey, g->ez_own, g->rank * g->ez_own, g->ez_glob, f->xg, f->wtab, out, d1, d2);                              \
-    f->last_kernel = 4;  \
+    *f->last_kernel = 4;  \
     } while (0)
     else if (!no_tile && c == 9)
         TP_CONV_ZRING(9);
@@ -464,12 +474,16 @@ static int filter_conv(tp_filter *f, double *out, const double *d1, const double
     else {
         TP_LAUNCH(k_conv_filter, dim3((int)((f->nel + BLK - 1) / BLK)), dim3(BLK), 0, g->stream, g->ex, g->ey,
                            g->ez_own, c, g->rank * g->ez_own, g->ez_glob, f->xg, f->wtab, out, d1, d2);
-        f->last_kernel = 5;
+        *f->last_kernel = 5;
     }
 #undef TP_CONV_TILED
     const double w3 = (2.0 * c + 1) * (2.0 * c + 1) * (2.0 * c + 1);
     count_launch(g, (16.0 + (d1 ? 8.0 : 0.0) + (d2 ? 8.0 : 0.0)) * f->nel, 2.0 * w3 * f->nel);
     return TP_OK;
+}
+static int filter_conv(tp_filter *f, double *out, const double *d1, const double *d2) {
+    const ConvArgs a = {f->grid, f->conn, f->wtab, f->xg, f->nel, f->lay, &f->last_kernel};
+    return conv_apply(&a, out, d1, d2);
 }
 static int filter_fill(tp_filter *f, const double *a, const double *b, int mode) {
     tp_grid *g = f->grid;

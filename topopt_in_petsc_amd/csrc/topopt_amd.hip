@@ -1803,6 +1803,11 @@ extern "C" int tp_elasticity_last_op_form(const tp_elasticity *e, int *form4) {
 #include "filter.h"
 
 // ===========================================================================
+// local volume constraint on the filter's convolution
+// ===========================================================================
+#include "localvol.h"
+
+// ===========================================================================
 // optimizer step around the path (MMA), SURVEY.md 8(f)-1
 // ===========================================================================
 #include "mma.h"

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import mpiio
-from .api import Filter, Grid, LinearElasticity, MMA, SolverOptions
+from .api import Filter, Grid, LinearElasticity, LocalVolume, MMA, SolverOptions
 
 
 @dataclass
@@ -69,6 +69,12 @@ class TopOpt:
     stress_P: float = 8.0
     stress_q: float = 0.5
     stress_case: int = 0
+    # local volume constraint: the p-norm (exponent local_volume_p) of the mean density in a ball of radius local_volume_R
+    # around every element held below local_volume as the LAST MMA constraint g = pn / local_volume - 1 (None: none, nothing
+    # changes); the constraints are ordered [volume, stress?, local]
+    local_volume: float = None
+    local_volume_R: float = None
+    local_volume_p: float = 16.0
     history: list = field(default_factory=list)
 
     def __post_init__(self):
@@ -76,6 +82,14 @@ class TopOpt:
             if not self.stress_limit > 0.0:
                 raise ValueError("stress_limit must be positive")
             self.m = max(self.m, 2)
+        self._k_local = None
+        if self.local_volume is not None:
+            if self.local_volume_R is None:
+                raise ValueError("local_volume needs local_volume_R")
+            if not self.local_volume > 0.0 or not self.local_volume_R > 0.0:
+                raise ValueError("local_volume and local_volume_R must be positive")
+            self._k_local = 2 if self.stress_limit is not None else 1
+            self.m = max(self.m, self._k_local + 1)
         nx, ny, nz = self.nxyz
         h = ((self.xc[1] - self.xc[0]) / (nx - 1), (self.xc[3] - self.xc[2]) / (ny - 1),
              (self.xc[5] - self.xc[4]) / (nz - 1))
@@ -91,6 +105,7 @@ class TopOpt:
             else:
                 self.physics.AddLoadCase(rhs, weight)
         self.filt = Filter(self.grid, self.filter, self.rmin)
+        self.localvol = LocalVolume(self.grid, self.local_volume_R) if self.local_volume is not None else None
         g = self.grid
         # TopOpt.cc:362-381: all design fields start at volfrac
         self.x = g.elem_vec(self.volfrac)
@@ -139,6 +154,10 @@ class TopOpt:
                                                                     self.stress_q, self.stress_P, self.stress_case)
             self.dgdx[1].div_(self.stress_limit)
             gxs.append(pnorm / self.stress_limit - 1.0)
+        if self.localvol is not None:       # last constraint, on xPhys alone
+            g_local, pn_local, rb_max = self.localvol.Constraint(self.xPhys, self.local_volume, self.local_volume_p,
+                                                                 dgdx=self.dgdx[self._k_local])
+            gxs.append(g_local)
         self.filt.Gradients(self.x, self.xTilde, self.dfdx, self.dgdx, self.projectionFilter, self.beta, self.eta)
         self.mma.SetOuterMovelimit(self.Xmin, self.Xmax, self.movlim, self.x, self.xmin, self.xmax)  # :81
         self.mma.Update(self.x, self.dfdx, gxs, self.dgdx, self.xmin, self.xmax)                 # :85
@@ -162,6 +181,8 @@ class TopOpt:
             rec["ksp_its"] = sum(self.physics.case_its)
         if self.stress_limit is not None:
             rec["stress_pnorm"], rec["stress_max"], rec["gx_stress"], rec["ksp_its_adjoint"] = pnorm, vm_max, gxs[1], its_adj
+        if self.localvol is not None:
+            rec["gx_local"], rec["local_pnorm"], rec["local_max"] = g_local, pn_local, rb_max
         self.history.append(rec)
         if verbose and self.rank == 0:
             print("It.: %i, True fx: %f, Scaled fx: %f, gx[0]: %f, ch.: %f, mnd.: %f, time: %f"

@@ -160,6 +160,13 @@ SYMBOLS = {
     "tp_vec_scale": (_i, [_vp, _vp, _d, _l]),
     "tp_vec_set": (_i, [_vp, _vp, _d, _l]),
     "tp_synth_density": (_i, [_vp, _vp, C.c_uint64]),
+    "tp_localvol_create": (_i, [C.POINTER(_vp), _vp, _d]),
+    "tp_localvol_destroy": (_i, [_vp]),
+    "tp_localvol_stencil_width": (_i, [_vp]),
+    "tp_localvol_get_count": (_i, [_vp, _vp]),
+    "tp_localvol_last_kernel": (_i, [_vp]),
+    "tp_localvol_mean": (_i, [_vp, _vp, _vp]),
+    "tp_localvol_constraint": (_i, [_vp, _vp, _d, _d, C.POINTER(_d), C.POINTER(_d), C.POINTER(_d), _vp, _vp]),
 }
 
 
