@@ -401,6 +401,28 @@ int tp_localvol_constraint(tp_localvol *lv, const double *xPhys, double alpha, d
         double *rhobar,     /* [dev, own elements]; may be NULL */
         double *dgdx);      /* [dev, own elements]; may be NULL */
 
+/* ---- overhang (self-support) filter (no reference counterpart; Langelaar 2016 / 2017) ---- */
+/* A "printed" density xi built from the blueprint density x layer by layer from the baseplate: every element takes the smooth
+ * minimum of its own density and the smooth maximum of the five elements that support it in the layer below (itself and its
+ * four in-plane neighbours: 45 degrees).  Build axis 1 (y) or 2 (z), sign +1 (baseplate at the lowest index) or -1; in-plane
+ * (i, r) = x and the remaining axis; Q = P + ln 5 / ln xi0; defaults P = 40, eps = 1e-4, xi0 = 0.5.
+ *   xi_0 = x_0;  S = sum over the cross of xi_{l-1}^P (outside the mesh: 0),  Xi = S^(1/Q),  d = x - Xi,  rho = sqrt(d^2 + eps),
+ *   xi = (x + Xi - rho + sqrt(eps)) / 2          (no clamp: min(x, Xi) <= xi <= min(x, Xi) + sqrt(eps) / 2)
+ * A filter, not a constraint: the responses are evaluated on xi and their gradients come back through the transpose of the
+ * forward sweep's Jacobian, which works in place on up to 8 vectors at once from coefficients the forward sweep left in the
+ * handle.  All arrays [dev, own elements].  z builds work on any number of slabs (the ranks sweep one after the other, the
+ * results are those of one rank bit for bit); TP_ERR_ARG for a y build on more than one rank and for any other axis.
+ * Both sweeps advance TP_OVERHANG_CHUNK layers per launch; every value gives the same bits. */
+typedef struct tp_overhang tp_overhang;
+int tp_overhang_create(tp_overhang **ov, tp_grid *g, int axis /*1 y, 2 z*/, int sign /*+1, -1*/);
+int tp_overhang_destroy(tp_overhang *ov);                       /* NULL: 0 */
+/* TP_ERR_ARG unless P >= 1, eps > 0, 0 < xi0 < 1 and Q >= 1; a forward call must follow before the next transpose */
+int tp_overhang_set_params(tp_overhang *ov, double P, double eps, double xi0);
+int tp_overhang_forward(tp_overhang *ov, const double *x, double *xi);   /* TP_ERR_ARG if x == xi */
+/* g[v] <- J^T g[v], v < nvec, 1 <= nvec <= 8; TP_ERR_ARG without a forward call on this handle before it */
+int tp_overhang_adjoint(tp_overhang *ov, int nvec, double *const *g);
+int tp_overhang_last_chunk(const tp_overhang *ov);              /* layers per launch of the last sweep */
+
 /* ---- MMA optimizer step on the device (MMA.cc) ------------ */
 typedef struct tp_mma tp_mma;
 /* MMA::MMA(n, m, x) (MMA.cc:108-190): a = 0, c = 1000, d = 0, asymptote factors 0.5 / 0.7 / 1.2.

@@ -739,6 +739,49 @@ class LocalVolume:
         return g.value, pn.value, mx.value
 
 
+class Overhang:
+    """Overhang (self-support) filter (tp_overhang): the printed density of a part built layer by layer along `build`
+    ("+z", "-z", "+y", "-y"; the baseplate lies at the low end for +), and the transpose of its Jacobian."""
+    BUILDS = {"+y": (1, 1), "-y": (1, -1), "+z": (2, 1), "-z": (2, -1)}
+
+    def __init__(self, grid, build="+z"):
+        if build not in self.BUILDS:
+            raise ValueError("build must be one of %s, got %r" % (", ".join(sorted(self.BUILDS)), build))
+        self.grid, self.L, self.build = grid, grid.L, build
+        self.handle = C.c_void_p()
+        _chk(self.L.tp_overhang_create(C.byref(self.handle), grid.handle, *self.BUILDS[build]), "tp_overhang_create")
+        grid._adopt(self)
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.L.tp_overhang_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def params(self, P=40.0, eps=1e-4, xi0=0.5):
+        _chk(self.L.tp_overhang_set_params(self.handle, P, eps, xi0), "tp_overhang_set_params")
+
+    def Forward(self, x, out):
+        """out = printed density of x (out must not be x); leaves the coefficients of the transpose in the handle"""
+        _chk(self.L.tp_overhang_forward(self.handle, _ptr(x), _ptr(out)), "tp_overhang_forward")
+        return out
+
+    def Adjoint(self, vecs):
+        """every tensor of the list (1 to 8) becomes J^T times itself, in place, in one sweep"""
+        ptrs = (C.c_void_p * len(vecs))(*[_ptr(v) for v in vecs])
+        _chk(self.L.tp_overhang_adjoint(self.handle, len(vecs), ptrs), "tp_overhang_adjoint")
+        return vecs
+
+    def last_chunk(self):
+        """layers per launch of the last sweep (TP_OVERHANG_CHUNK)"""
+        return self.L.tp_overhang_last_chunk(self.handle)
+
+
 class MMA:
     """MMA (MMA.h:29-140) on the device: the design vectors stay in HBM."""
 

@@ -293,6 +293,12 @@ inline bool sw_coarse_run() {
 inline bool sw_no_coarse_xcd() { return sw_set("TP_NO_COARSE_XCD"); }
 // TP_NO_LANCZOS_XCD set (default on): the coarsest level's Lanczos run as a chain of launches, not one launch on one XCD
 inline bool sw_no_lanczos_xcd() { return sw_set("TP_NO_LANCZOS_XCD"); }
+// TP_OVERHANG_CHUNK=1|2|4|8 (default 4, the fastest measured; any other value counts as unset): layers per launch of the overhang filter's two sweeps
+// (overhang.h); every value gives the same bits, tp_overhang_last_chunk reports what ran
+inline int sw_overhang_chunk() {
+    const int c = sw_int("TP_OVERHANG_CHUNK", 4);
+    return (c == 1 || c == 2 || c == 4 || c == 8) ? c : 4;
+}
 // TP_NO_GRAPH set (default graphs): the Lanczos chains are enqueued, not captured and replayed.  Read per call by
 // lanczos_graph_replayable; lanczos_graph latches it on its first run (mg_spectra.h), as before.
 inline bool sw_no_graph() { return sw_set("TP_NO_GRAPH"); }

@@ -1808,6 +1808,11 @@ extern "C" int tp_elasticity_last_op_form(const tp_elasticity *e, int *form4) {
 #include "localvol.h"
 
 // ===========================================================================
+// overhang (self-support) filter: layer sweeps along the build axis
+// ===========================================================================
+#include "overhang.h"
+
+// ===========================================================================
 // optimizer step around the path (MMA), SURVEY.md 8(f)-1
 // ===========================================================================
 #include "mma.h"

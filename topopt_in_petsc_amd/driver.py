@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import mpiio
-from .api import Filter, Grid, LinearElasticity, LocalVolume, MMA, SolverOptions
+from .api import Filter, Grid, LinearElasticity, LocalVolume, MMA, Overhang, SolverOptions
 
 
 @dataclass
@@ -75,9 +75,15 @@ class TopOpt:
     local_volume: float = None
     local_volume_R: float = None
     local_volume_p: float = 16.0
+    # overhang (self-support) filter: "+z", "-z", "+y" or "-y", the build direction of a part printed layer by layer.  Every
+    # response is evaluated on xPrint = Overhang.Forward(xPhys) and its gradient comes back through Overhang.Adjoint (None:
+    # xPrint is xPhys itself, nothing changes)
+    overhang: str = None
     history: list = field(default_factory=list)
 
     def __post_init__(self):
+        if self.overhang is not None and self.overhang not in Overhang.BUILDS:
+            raise ValueError("overhang must be None or one of %s, got %r" % (", ".join(sorted(Overhang.BUILDS)), self.overhang))
         if self.stress_limit is not None:
             if not self.stress_limit > 0.0:
                 raise ValueError("stress_limit must be positive")
@@ -106,10 +112,12 @@ class TopOpt:
                 self.physics.AddLoadCase(rhs, weight)
         self.filt = Filter(self.grid, self.filter, self.rmin)
         self.localvol = LocalVolume(self.grid, self.local_volume_R) if self.local_volume is not None else None
+        self.overhang_filter = Overhang(self.grid, self.overhang) if self.overhang is not None else None
         g = self.grid
         # TopOpt.cc:362-381: all design fields start at volfrac
         self.x = g.elem_vec(self.volfrac)
         self.xTilde, self.xPhys = g.elem_vec(self.volfrac), g.elem_vec(self.volfrac)
+        self.xPrint = g.elem_vec(self.volfrac) if self.overhang_filter is not None else self.xPhys
         self.dfdx, self.dgdx = g.elem_vec(), [g.elem_vec() for _ in range(self.m)]
         self.xmin, self.xmax, self.xold = g.elem_vec(), g.elem_vec(), g.elem_vec(self.volfrac)
         if self.aMMA is None and self.cMMA is None and self.dMMA is None:
@@ -137,27 +145,35 @@ class TopOpt:
             self.ReadRestartFiles(self.restartFileVec, self.restartFileItr, self.restartFileVecSol)
         # main.cc:48
         self.filt.FilterProject(self.x, self.xTilde, self.xPhys, self.projectionFilter, self.beta, self.eta)
+        self._print()
+
+    def _print(self):
+        """xPrint follows every FilterProject"""
+        if self.overhang_filter is not None:
+            self.overhang_filter.Forward(self.xPhys, self.xPrint)
 
     def step(self, verbose=False):
         """one pass of the loop body, main.cc:54-111; returns the record of this iteration"""
         self.itr += 1
         t1 = time.perf_counter()
         fx, gx = self.physics.ComputeObjectiveConstraintsSensitivities(
-            self.dfdx, self.dgdx[0], self.xPhys, self.Emin, self.Emax, self.penal, self.volfrac)   # main.cc:62
+            self.dfdx, self.dgdx[0], self.xPrint, self.Emin, self.Emax, self.penal, self.volfrac)   # main.cc:62
         if self.itr == 1:
             self.fscale = 10.0 / fx                                                              # :68-70
         fxs = fx * self.fscale
         self.dfdx.mul_(self.fscale)                                                              # :73
         gxs = [gx]
         if self.stress_limit is not None:   # second constraint on the assembly and state of the solve above
-            pnorm, vm_max, its_adj = self.physics.StressSensitivity(self.dgdx[1], self.xPhys, self.Emin, self.Emax, self.penal,
+            pnorm, vm_max, its_adj = self.physics.StressSensitivity(self.dgdx[1], self.xPrint, self.Emin, self.Emax, self.penal,
                                                                     self.stress_q, self.stress_P, self.stress_case)
             self.dgdx[1].div_(self.stress_limit)
             gxs.append(pnorm / self.stress_limit - 1.0)
-        if self.localvol is not None:       # last constraint, on xPhys alone
-            g_local, pn_local, rb_max = self.localvol.Constraint(self.xPhys, self.local_volume, self.local_volume_p,
+        if self.localvol is not None:       # last constraint, on the density alone
+            g_local, pn_local, rb_max = self.localvol.Constraint(self.xPrint, self.local_volume, self.local_volume_p,
                                                                  dgdx=self.dgdx[self._k_local])
             gxs.append(g_local)
+        if self.overhang_filter is not None:   # d/dxPrint -> d/dxPhys, all of them in one sweep
+            self.overhang_filter.Adjoint([self.dfdx] + self.dgdx)
         self.filt.Gradients(self.x, self.xTilde, self.dfdx, self.dgdx, self.projectionFilter, self.beta, self.eta)
         self.mma.SetOuterMovelimit(self.Xmin, self.Xmax, self.movlim, self.x, self.xmin, self.xmax)  # :81
         self.mma.Update(self.x, self.dfdx, gxs, self.dgdx, self.xmin, self.xmax)                 # :85
@@ -167,7 +183,8 @@ class TopOpt:
         if self.projectionFilter:                                                                # :93-95
             self._increase_beta(gx, ch)
         self.filt.FilterProject(self.x, self.xTilde, self.xPhys, self.projectionFilter, self.beta, self.eta)  # :98
-        mnd = self.filt.GetMND(self.xPhys)                                                       # :102
+        self._print()
+        mnd = self.filt.GetMND(self.xPrint)                                                      # :102
         torch.cuda.synchronize()
         t2 = time.perf_counter()
         rec = dict(itr=self.itr, fx=fx, fx_scaled=fxs, gx=gx, ch=ch, mnd=mnd, time=t2 - t1,
@@ -183,6 +200,8 @@ class TopOpt:
             rec["stress_pnorm"], rec["stress_max"], rec["gx_stress"], rec["ksp_its_adjoint"] = pnorm, vm_max, gxs[1], its_adj
         if self.localvol is not None:
             rec["gx_local"], rec["local_pnorm"], rec["local_max"] = g_local, pn_local, rb_max
+        if self.overhang_filter is not None:
+            rec["print_loss"] = self._mean(self.xPhys - self.xPrint)
         self.history.append(rec)
         if verbose and self.rank == 0:
             print("It.: %i, True fx: %f, Scaled fx: %f, gx[0]: %f, ch.: %f, mnd.: %f, time: %f"
@@ -198,6 +217,16 @@ class TopOpt:
         parts = [None] * self.nranks
         dist.all_gather_object(parts, a)
         return np.concatenate(parts)
+
+    def _mean(self, t):
+        """mean over the elements of all ranks (the slabs are equally thick)"""
+        m = float(t.mean())
+        if self.nranks == 1:
+            return m
+        import torch.distributed as dist
+        parts = [None] * self.nranks
+        dist.all_gather_object(parts, m)
+        return sum(parts) / self.nranks
 
     def _own(self, a):
         n = self.grid.part.n_own_elems
@@ -242,7 +271,7 @@ class TopOpt:
 
     def WriteVTK(self, itr):
         if self._out is not None:
-            self._out.WriteVTK(self.physics.U, self.x, self.xTilde, self.xPhys, itr)
+            self._out.WriteVTK(self.physics.U, self.x, self.xTilde, self.xPrint, itr)
 
     def _increase_beta(self, gx, ch):
         """Filter::IncreaseBeta, Filter.cc:268-288"""

@@ -166,6 +166,12 @@ SYMBOLS = {
     "tp_localvol_get_count": (_i, [_vp, _vp]),
     "tp_localvol_last_kernel": (_i, [_vp]),
     "tp_localvol_mean": (_i, [_vp, _vp, _vp]),
+    "tp_overhang_create": (_i, [C.POINTER(_vp), _vp, _i, _i]),
+    "tp_overhang_destroy": (_i, [_vp]),
+    "tp_overhang_set_params": (_i, [_vp, _d, _d, _d]),
+    "tp_overhang_forward": (_i, [_vp, _vp, _vp]),
+    "tp_overhang_adjoint": (_i, [_vp, _i, C.POINTER(_vp)]),
+    "tp_overhang_last_chunk": (_i, [_vp]),
     "tp_localvol_constraint": (_i, [_vp, _vp, _d, _d, C.POINTER(_d), C.POINTER(_d), C.POINTER(_d), _vp, _vp]),
 }
 
