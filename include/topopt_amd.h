@@ -295,6 +295,23 @@ int tp_elasticity_stress(tp_elasticity *e, const double *U, const double *xPhys,
         double *dpdx,     /* [dev, own elements] explicit part; may be NULL */
         double *adj_rhs); /* [dev, local nodes*3] d pnorm / dU on owned planes; may be NULL */
 int tp_elasticity_get_stress_form(const tp_elasticity *e, double *m_host_576);
+/* Self-weight: a body force b = (b_x, b_y, b_z) per unit volume at full density (rho g) that moves with the material.
+ * V_e = hx hy hz; mass interpolation m(x) = x for x >= x_low (or x_low = 0), m(x) = x t^5 (6 - 5 t) with t = x / x_low below
+ * (m' = t^5 (36 - 35 t); C1 at x_low, m / x^p bounded), x >= 0.
+ *   load:         rhs_n = rhs_base_n + (V_e / 8) b sum_{e contains n} m(x_e)   on the OWNED node planes (ghost planes are left
+ *                 as they are; supports not applied -- tp_elasticity_solve multiplies by N); rhs_base NULL = 0, rhs == rhs_base
+ *                 works in place.  A gather in one fixed order: the same bits on any number of slabs.
+ *   sensitivity:  dfdx_e += scale m'(x_e) (V_e / 8) sum_l w_l sum_{a = 1..8} sum_c b_c N_{a,c} V_l,{a,c}   (the supports N of the
+ *                 handle applied inside; the ghost planes of every distinct V_l are refreshed first).
+ * With K u = N (F + f(x)):  d(u^T K u)/dx = tp_elasticity_response's dfdx + the term with V = u, scale = 2; a response with
+ * adjoint state lam gains the term with V = lam, scale = 1.  Neither call reduces anything or makes the host wait.
+ * TP_ERR_ARG unless e, xPhys, b3, rhs / dfdx and every V[l] are given, 0 <= x_low < 1, b3 and scale are finite and
+ * 1 <= ncase <= TP_MAX_CASES; TP_ERR_STATE before the supports are set. */
+int tp_elasticity_body_load(tp_elasticity *e, const double *xPhys /*[dev, own elements]*/, const double *b3 /*host, 3*/,
+                            double x_low, const double *rhs_base /*[dev, local nodes*3] or NULL*/, double *rhs /*[dev]*/);
+int tp_elasticity_body_sensitivity(tp_elasticity *e, int ncase, const double *const *V /*host array of [dev] pointers*/,
+                            const double *w /*host, NULL = all 1*/, const double *xPhys, const double *b3, double x_low,
+                            double scale, double *dfdx /*[dev, own elements], added to*/);
 /* introspection for parity tests */
 /* KSPSetTolerances (LinearElasticity.cc:646); a negative value keeps the current one (PETSC_DEFAULT) */
 int tp_elasticity_set_tolerances(tp_elasticity *le, double rtol, double atol, double dtol, int max_it);

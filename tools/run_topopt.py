@@ -1,12 +1,14 @@
 #!/usr/bin/env python
 """End-to-end run of the reference's optimisation loop on the MI355X path.
-usage: run_topopt.py [--loadcase top[:weight]]... [--stress-limit L [--stress-p P] [--stress-q q]] [--local-volume ALPHA:R] [--overhang +z|-z|+y|-y] ex ey ez nlvls n_iter [filter [nsmooth ncoarse]]
+usage: run_topopt.py [--loadcase top[:weight]]... [--stress-limit L [--stress-p P] [--stress-q q]] [--local-volume ALPHA:R] [--overhang +z|-z|+y|-y] [--self-weight bx,by,bz[:xlow] [--no-point-load]] ex ey ez nlvls n_iter [filter [nsmooth ncoarse]]
 (e.g. 128 128 128 5 20 1 2 45: the cycle of bench.py; --loadcase top:0.5 adds the line load on the upper edge as a second load
 case of weight 0.5 -- the objective becomes the weighted sum of the cases' compliances; --stress-limit L holds the von Mises
 p-norm of load case 0 below L as a second constraint, exponent --stress-p (8), stress relaxation x^q with --stress-q (0.5); --local-volume ALPHA:R holds the mean density in a ball of
 radius R (a length, the element size is 1/ey) around every element below ALPHA through one p-norm constraint, exponent 16, as
 the last constraint; --overhang DIR evaluates every response on the printed density of a part built layer by layer along DIR, the
-overhang filter of DESIGN 4.11)"""
+overhang filter of DESIGN 4.11; --self-weight bx,by,bz[:xlow] adds the structure's own weight, a body force (per unit volume at full
+density) that moves with the design, the mass of elements below xlow (0.1) damped, DESIGN 4.12 -- with --no-point-load it is the only
+load)"""
 import os
 import sys
 
@@ -83,11 +85,27 @@ if local_volume is not None:
         sys.exit("--local-volume needs ALPHA:R, got %r" % local_volume)
     local = dict(local_volume=float(alpha), local_volume_R=float(radius))
 overhang, sys.argv[1:] = _text_option(sys.argv[1:], "--overhang")
+self_weight, sys.argv[1:] = _text_option(sys.argv[1:], "--self-weight")
+no_point_load = "--no-point-load" in sys.argv[1:]
+sys.argv[1:] = [a for a in sys.argv[1:] if a != "--no-point-load"]
+body = {}
+if self_weight is not None:
+    vec, _, xlow = self_weight.partition(":")
+    try:
+        body = dict(body_force=tuple(float(v) for v in vec.split(",")), body_force_xlow=float(xlow) if xlow else 0.1)
+    except ValueError:
+        sys.exit("--self-weight needs bx,by,bz[:xlow], got %r" % self_weight)
+    if len(body["body_force"]) != 3:
+        sys.exit("--self-weight needs bx,by,bz[:xlow], got %r" % self_weight)
+if no_point_load:
+    if not body:
+        sys.exit("--no-point-load needs --self-weight")
+    body["point_load"] = False
 ex, ey, ez, nlv, nit = [int(v) for v in sys.argv[1:6]]
 flt = int(sys.argv[6]) if len(sys.argv) > 6 else 1
 h = 1.0 / ey
 opt = tp.TopOpt(nxyz=(ex + 1, ey + 1, ez + 1), xc=(0, ex * h, 0, 1, 0, ez * h), nlvls=nlv, rmin=2.56 * h, filter=flt,
-                loadcases=loadcases or None, **stress, **local, overhang=overhang,
+                loadcases=loadcases or None, **stress, **local, overhang=overhang, **body,
                 solver=tp.SolverOptions(nlvls=nlv, **(dict(nsmooth=int(sys.argv[7]), ncoarse=int(sys.argv[8])) if len(sys.argv) > 8 else {})))
 print("# %dx%dx%d elements, %d DOF, %d MG levels, filter %d, rmin %.4f" % (ex, ey, ez, 3 * (ex + 1) * (ey + 1) * (ez + 1), nlv, flt, 2.56 * h))
 for it in range(nit):
@@ -100,5 +118,7 @@ for it in range(nit):
               % (r["stress_pnorm"], r["stress_max"], r["gx_stress"], r["ksp_its_adjoint"]), flush=True)
     if "print_loss" in r:
         print("Overhang:      build %s, mean(xPhys - xPrint): %f" % (overhang, r["print_loss"]), flush=True)
+    if "body_share" in r:
+        print("Self-weight:   b: %s, x_low: %g, body load's share of the compliance: %f" % (",".join("%g" % v for v in opt.body_force), opt.body_force_xlow, r["body_share"]), flush=True)
     if "gx_local" in r:
         print("Local volume:  p-norm: %f, max: %f, gx[%d]: %f" % (r["local_pnorm"], r["local_max"], opt.m - 1, r["gx_local"]), flush=True)

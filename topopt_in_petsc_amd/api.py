@@ -30,6 +30,21 @@ def _chk(code, where):
         raise TopOptError(code, where)
 
 
+def check_body_force(b, x_low):
+    """-> ((b_x, b_y, b_z), x_low) as floats; ValueError unless b is three finite numbers and 0 <= x_low < 1"""
+    import math
+    try:
+        b = tuple(float(v) for v in b)
+        x_low = float(x_low)
+    except (TypeError, ValueError):
+        raise ValueError("body force: need three numbers and a number x_low, got %r, %r" % (b, x_low))
+    if len(b) != 3 or not all(math.isfinite(v) for v in b):
+        raise ValueError("body force: need three finite numbers (b_x, b_y, b_z), got %r" % (b,))
+    if not 0.0 <= x_low < 1.0:
+        raise ValueError("body force: x_low must lie in [0, 1), got %r" % (x_low,))
+    return b, x_low
+
+
 def _ptr(t):
     if t is None:
         return None
@@ -282,6 +297,8 @@ class LinearElasticity:
         # stress constraint: the adjoint state persists like the states (warm start); allocated by the first StressSensitivity
         self.lam = self._stress_dpdx = self._stress_rhs = None
         self.adjoint_its, self.adjoint_rnorm, self.adjoint_bnorm = 0, 0.0, 0.0
+        # self-weight (SetBodyForce): None = off; the total loads F_l + f(xPhys) live in buffers of their own, made on first use
+        self.body_force, self.body_xlow, self._case_total = None, 0.1, []
 
     def close(self):
         if getattr(self, "handle", None):
@@ -405,10 +422,51 @@ class LinearElasticity:
         _chk(self.L.tp_elasticity_apply_krylov(self.handle, _ptr(u), _ptr(y)), "tp_elasticity_apply_krylov")
         return y
 
-    def KSPSolve(self, hist_cap=0, case=0):
-        """solve load case `case` on the last assembly, warm-started from that case's own state"""
+    # ---- self-weight: a body force that moves with the material ----
+    def SetBodyForce(self, b, x_low=0.1):
+        """b = (b_x, b_y, b_z), the body force per unit volume at full density (rho g); below x_low the mass is damped as
+        m(x) = x t^5 (6 - 5 t), t = x / x_low (include/topopt_amd.h).  From now on SolveState solves on F_l + f(xPhys) and the
+        sensitivities carry the load's term.  None switches it off again."""
+        if b is None:
+            self.body_force, self._case_total = None, []
+            return
+        self.body_force, self.body_xlow = check_body_force(b, x_low)
+
+    def _body3(self):
+        if self.body_force is None:
+            raise TopOptError(2, "self-weight (no body force set: SetBodyForce)")
+        return (C.c_double * 3)(*self.body_force)
+
+    def BodyLoad(self, xPhys, out, base=None):
+        """out = base + f(xPhys) on the owned node planes (base None: f alone; out may be base); ghost planes stay"""
+        _chk(self.L.tp_elasticity_body_load(self.handle, _ptr(xPhys), self._body3(), self.body_xlow, _ptr(base), _ptr(out)),
+             "tp_elasticity_body_load")
+        return out
+
+    def BodySensitivity(self, V_list, w, xPhys, scale, dfdx):
+        """dfdx += scale * sum_l w_l d(v_l^T N f)/dxPhys (w None: all weights 1); nothing is reduced, the host does not wait"""
+        n = len(V_list)
+        Va = (C.c_void_p * max(n, 1))(*[_ptr(v) for v in V_list])
+        wa = None if w is None else (C.c_double * max(n, 1))(*[float(v) for v in w])
+        _chk(self.L.tp_elasticity_body_sensitivity(self.handle, n, Va, wa, _ptr(xPhys), self._body3(), self.body_xlow, float(scale),
+                                                   _ptr(dfdx)), "tp_elasticity_body_sensitivity")
+
+    def TotalRHS(self, case):
+        """F_case + f(xPhys) of the last SolveState with a body force set (LoadCaseRHS keeps returning the fixed load)"""
+        return self._case_total[case]
+
+    def _form_totals(self, xPhys):
+        while len(self._case_total) < self.ncases:
+            self._case_total.append(self.grid.node_vec(3))
+        for rhs, total in zip(self._case_rhs, self._case_total):
+            total.copy_(rhs)   # (the ghost planes too)
+            self.BodyLoad(xPhys, total, base=total)
+
+    def KSPSolve(self, hist_cap=0, case=0, rhs=None):
+        """solve load case `case` on the last assembly, warm-started from that case's own state (rhs: another right-hand side
+        than the case's fixed load)"""
         import numpy as np
-        RHS, U = self._case_rhs[case], self._case_U[case]
+        RHS, U = self._case_rhs[case] if rhs is None else rhs, self._case_U[case]
         its, rn, bn = C.c_int(), C.c_double(), C.c_double()
         hist = np.zeros(max(hist_cap, 1))
         import time
@@ -425,6 +483,11 @@ class LinearElasticity:
     def SolveState(self, xPhys, Emin, Emax, penal, hist_cap=0):
         """LinearElasticity.cc:182-223; several load cases: one assembly, then every case in index order"""
         self.AssembleStiffnessMatrix(xPhys, Emin, Emax, penal)
+        if self.body_force is not None:
+            self._form_totals(xPhys)
+            for case in range(self.ncases):
+                its = self.KSPSolve(hist_cap, case, rhs=self._case_total[case])
+            return its
         its = self.KSPSolve(hist_cap)
         for case in range(1, self.ncases):
             its = self.KSPSolve(hist_cap, case)
@@ -484,6 +547,8 @@ class LinearElasticity:
         self.adjoint_its, self.adjoint_rnorm, self.adjoint_bnorm = its.value, rn.value, bn.value
         _chk(rc, "tp_elasticity_solve (adjoint)")
         self.Response([U], [self.lam], None, xPhys, Emin, Emax, penal, 0.0, dfdx=dsdx, sums=False)
+        if self.body_force is not None:   # d pnorm/dx = dpdx - lam^T (dK/dx u - df/dx)
+            self.BodySensitivity([self.lam], None, xPhys, 1.0, dsdx)
         _chk(self.L.tp_vec_axpby(self.grid.handle, _ptr(dsdx), 1.0, _ptr(self._stress_dpdx), 1.0, dsdx.numel()), "tp_vec_axpby")
         return pn, mx, its.value
 
@@ -497,6 +562,14 @@ class LinearElasticity:
     def ComputeObjectiveConstraintsSensitivities(self, dfdx, dgdx, xPhys, Emin, Emax, penal, volfrac, hist_cap=0):
         """LinearElasticity.cc:363-445 -> (fx, gx); several load cases: fx = sum_l w_l u_l^T K u_l (last_f_case: the f_l)"""
         self.SolveState(xPhys, Emin, Emax, penal, hist_cap)
+        if self.body_force is not None:   # u^T K u = (F + f)^T u as it stands; dfdx gains 2 d(u^T N f)/dx per case
+            if self.ncases > 1:
+                fx, gx, self.last_f_case = self.Response(self._case_U, None, self.case_weight, xPhys, Emin, Emax, penal, volfrac,
+                                                         dfdx, dgdx)
+            else:
+                fx, gx = self.Objective(xPhys, Emin, Emax, penal, volfrac, dfdx, dgdx)
+            self.BodySensitivity(self._case_U, self.case_weight, xPhys, 2.0, dfdx)
+            return fx, gx
         if self.ncases > 1:
             fx, gx, self.last_f_case = self.Response(self._case_U, None, self.case_weight, xPhys, Emin, Emax, penal, volfrac,
                                                      dfdx, dgdx)
@@ -516,6 +589,14 @@ class LinearElasticity:
 
     def ComputeSensitivities(self, dfdx, dgdx, xPhys, Emin, Emax, penal, volfrac=0.0):
         """LinearElasticity.cc:299-361: dfdx, dgdx of the current state U (no solve); several load cases: of all states"""
+        if self.body_force is not None:
+            if self.ncases > 1:
+                self.Response(self._case_U, None, self.case_weight, xPhys, Emin, Emax, penal, volfrac, dfdx, dgdx, sums=False)
+            else:
+                _chk(self.L.tp_elasticity_sensitivities(self.handle, _ptr(self.U), _ptr(xPhys), Emin, Emax, penal, _ptr(dfdx),
+                                                        _ptr(dgdx) if dgdx is not None else None), "tp_elasticity_sensitivities")
+            self.BodySensitivity(self._case_U, self.case_weight, xPhys, 2.0, dfdx)
+            return
         if self.ncases > 1:
             self.Response(self._case_U, None, self.case_weight, xPhys, Emin, Emax, penal, volfrac, dfdx, dgdx, sums=False)
             return

@@ -538,6 +538,7 @@ struct tp_elasticity {
     double *d_sx = nullptr;    // tp_elasticity_stress: per-element scratch between its passes, own + ghost-above layer (first use)
     double *d_resp = nullptr;  // block partials of tp_elasticity_response, (TP_MAX_CASES + 1) x resp_nb, allocated by its first sums
     long resp_nb = 0;
+    double *d_xg = nullptr;    // tp_elasticity_body_load: the upper neighbour's first own layer of xPhys (slabs, first use)
     bool have_bc, assembled;
 };
 
@@ -702,7 +703,7 @@ extern "C" int tp_elasticity_destroy(tp_elasticity *e) {
                     (void *)e->d_flagged, (void *)e->d_colmask, (void *)e->d_flag_all, (void *)e->d_corr_nodes,
                     (void *)e->d_corr_adj, (void *)e->d_dK, (void *)e->d_corr, (void *)e->d_corr_tmp, (void *)e->d_KelF,
                     (void *)e->d_fidx1, (void *)e->d_M2, (void *)e->d_flag2, (void *)e->d_list2, (void *)e->d_resp,
-                    (void *)e->d_VM, (void *)e->d_sx})
+                    (void *)e->d_VM, (void *)e->d_sx, (void *)e->d_xg})
         (void)hipFree(p);
     delete e;
     return TP_OK;
@@ -1639,6 +1640,9 @@ extern "C" int tp_elasticity_stress(tp_elasticity *e, const double *U, const dou
     count_launch(g, 48.0 * nown + 8.0 * nel, 2.0 * 8 * (63 + 3) * nown);
     return TP_OK;
 }
+
+// ---- self-weight: design-dependent body force, its nodal load and its sensitivity term
+#include "bodyforce.h"
 
 extern "C" int tp_elasticity_set_tolerances(tp_elasticity *e, double rtol, double atol, double dtol, int max_it) {
     if (!e) return TP_ERR_ARG;   // KSPSetTolerances (LinearElasticity.cc:646); negative = keep (PETSC_DEFAULT)

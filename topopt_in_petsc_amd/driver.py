@@ -14,7 +14,9 @@ import numpy as np
 import torch
 
 from . import mpiio
-from .api import Filter, Grid, LinearElasticity, LocalVolume, MMA, Overhang, SolverOptions
+import ctypes as C
+
+from .api import Filter, Grid, LinearElasticity, LocalVolume, MMA, Overhang, SolverOptions, _chk, _ptr, check_body_force
 
 
 @dataclass
@@ -79,11 +81,23 @@ class TopOpt:
     # response is evaluated on xPrint = Overhang.Forward(xPhys) and its gradient comes back through Overhang.Adjoint (None:
     # xPrint is xPhys itself, nothing changes)
     overhang: str = None
+    # self-weight: body_force = (b_x, b_y, b_z), the body force per unit volume at full density (rho g), as a load that moves
+    # with xPrint beside the fixed ones; the mass of elements below body_force_xlow is damped.  point_load=False
+    # zeroes case 0's fixed load: a part that carries its own weight only (None: no body force, nothing changes)
+    body_force: tuple = None
+    body_force_xlow: float = 0.1
+    point_load: bool = True
     history: list = field(default_factory=list)
 
     def __post_init__(self):
         if self.overhang is not None and self.overhang not in Overhang.BUILDS:
             raise ValueError("overhang must be None or one of %s, got %r" % (", ".join(sorted(Overhang.BUILDS)), self.overhang))
+        if self.body_force is not None:
+            self.body_force, self.body_force_xlow = check_body_force(self.body_force, self.body_force_xlow)
+        else:
+            check_body_force((0.0, 0.0, 0.0), self.body_force_xlow)
+            if not self.point_load:
+                raise ValueError("point_load=False needs a body_force: the structure would carry no load")
         if self.stress_limit is not None:
             if not self.stress_limit > 0.0:
                 raise ValueError("stress_limit must be positive")
@@ -103,6 +117,11 @@ class TopOpt:
         so = self.solver or SolverOptions(nlvls=self.nlvls, nu=self.nu)
         self.physics = LinearElasticity(self.grid, so)
         self.physics.SetUpLoadAndBC()
+        if self.body_force is not None:
+            self.physics.SetBodyForce(self.body_force, self.body_force_xlow)
+            self._f_body = self.grid.node_vec(3)
+            if not self.point_load:
+                self.physics.RHS.zero_()
         for rhs, weight in (self.loadcases or ()):
             if isinstance(rhs, str):
                 if rhs != "top":
@@ -147,6 +166,17 @@ class TopOpt:
         self.filt.FilterProject(self.x, self.xTilde, self.xPhys, self.projectionFilter, self.beta, self.eta)
         self._print()
 
+    def _body_share(self):
+        """(f_body^T u) / (f_total^T u) of load case 0 on the state just solved, owned node range, all ranks"""
+        ph, sl = self.physics, self.grid.part.owned_slice(3)
+        ph.BodyLoad(self.xPrint, self._f_body)
+        u, out = ph.U[sl], []
+        for f in (self._f_body[sl], ph.TotalRHS(0)[sl]):
+            v = C.c_double()
+            _chk(self.grid.L.tp_vec_dot(self.grid.handle, _ptr(f), _ptr(u), u.numel(), C.byref(v)), "tp_vec_dot")
+            out.append(v.value)
+        return out[0] / out[1]
+
     def _print(self):
         """xPrint follows every FilterProject"""
         if self.overhang_filter is not None:
@@ -158,6 +188,8 @@ class TopOpt:
         t1 = time.perf_counter()
         fx, gx = self.physics.ComputeObjectiveConstraintsSensitivities(
             self.dfdx, self.dgdx[0], self.xPrint, self.Emin, self.Emax, self.penal, self.volfrac)   # main.cc:62
+        if self.body_force is not None:   # (before xPrint moves on)
+            body_share = self._body_share()
         if self.itr == 1:
             self.fscale = 10.0 / fx                                                              # :68-70
         fxs = fx * self.fscale
@@ -202,6 +234,8 @@ class TopOpt:
             rec["gx_local"], rec["local_pnorm"], rec["local_max"] = g_local, pn_local, rb_max
         if self.overhang_filter is not None:
             rec["print_loss"] = self._mean(self.xPhys - self.xPrint)
+        if self.body_force is not None:
+            rec["body_share"] = body_share
         self.history.append(rec)
         if verbose and self.rank == 0:
             print("It.: %i, True fx: %f, Scaled fx: %f, gx[0]: %f, ch.: %f, mnd.: %f, time: %f"

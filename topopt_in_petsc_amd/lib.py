@@ -107,6 +107,8 @@ SYMBOLS = {
                                     C.POINTER(_d), C.POINTER(_d), _vp, _vp]),
     "tp_elasticity_stress": (_i, [_vp, _vp, _vp, _d, _d, _d, _vp, C.POINTER(_d), C.POINTER(_d), _vp, _vp]),
     "tp_elasticity_get_stress_form": (_i, [_vp, _vp]),
+    "tp_elasticity_body_load": (_i, [_vp, _vp, C.POINTER(_d), _d, _vp, _vp]),
+    "tp_elasticity_body_sensitivity": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_d), _vp, C.POINTER(_d), _d, _d, _vp]),
     "tp_elasticity_petsc_options": (_i, [_vp, C.c_char_p, C.c_size_t]),
     "tp_elasticity_level_count": (_i, [_vp]),
     "tp_elasticity_level_nodes": (_l, [_vp, _i]),
