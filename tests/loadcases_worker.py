@@ -72,11 +72,5 @@ def response_mode(rank, world):
 
 
 if __name__ == "__main__":
-    mode = sys.argv[1]
-    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-    dist.init_process_group("gloo")
-    rank, world = dist.get_rank(), dist.get_world_size()
-    try:
-        {"response": response_mode}[mode](rank, world)
-    finally:
-        dist.destroy_process_group()
+    from tests.slab_launch import run_modes
+    run_modes({"response": response_mode})

@@ -86,14 +86,8 @@ def toowide_mode(rank, world):
 
 
 if __name__ == "__main__":
-    mode = sys.argv[1]
-    if mode == "kernel":
+    if sys.argv[1] == "kernel":
         kernel_mode()
     else:
-        import torch.distributed as dist
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        dist.init_process_group("gloo")
-        try:
-            {"slabs": slabs_mode, "toowide": toowide_mode}[mode](dist.get_rank(), dist.get_world_size())
-        finally:
-            dist.destroy_process_group()
+        from tests.slab_launch import run_modes
+        run_modes({"slabs": slabs_mode, "toowide": toowide_mode})

@@ -267,11 +267,5 @@ def gpu_giveup_mode(rank, world):
 
 
 if __name__ == "__main__":
-    mode = sys.argv[1]
-    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-    dist.init_process_group("gloo")
-    rank, world = dist.get_rank(), dist.get_world_size()
-    try:
-        {"cpu": cpu_mode, "gpu": gpu_mode, "gpu_randbc": gpu_randbc_mode, "gpu_giveup": gpu_giveup_mode}[mode](rank, world)
-    finally:
-        dist.destroy_process_group()
+    from tests.slab_launch import run_modes
+    run_modes({"cpu": cpu_mode, "gpu": gpu_mode, "gpu_randbc": gpu_randbc_mode, "gpu_giveup": gpu_giveup_mode})

@@ -61,11 +61,5 @@ def ybuild_mode(rank, world):
 
 
 if __name__ == "__main__":
-    mode = sys.argv[1]
-    import torch.distributed as dist
-    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-    dist.init_process_group("gloo")
-    try:
-        {"slabs": slabs_mode, "ybuild": ybuild_mode}[mode](dist.get_rank(), dist.get_world_size())
-    finally:
-        dist.destroy_process_group()
+    from tests.slab_launch import run_modes
+    run_modes({"slabs": slabs_mode, "ybuild": ybuild_mode})

@@ -109,10 +109,5 @@ def driver_mode(rank, world):
 
 
 if __name__ == "__main__":
-    mode = sys.argv[1]
-    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-    dist.init_process_group("gloo")
-    try:
-        {"kernels": kernels_mode, "driver": driver_mode}[mode](dist.get_rank(), dist.get_world_size())
-    finally:
-        dist.destroy_process_group()
+    from tests.slab_launch import run_modes
+    run_modes({"kernels": kernels_mode, "driver": driver_mode})

@@ -66,11 +66,5 @@ def stress_mode(rank, world):
 
 
 if __name__ == "__main__":
-    mode = sys.argv[1]
-    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-    dist.init_process_group("gloo")
-    rank, world = dist.get_rank(), dist.get_world_size()
-    try:
-        {"stress": stress_mode}[mode](rank, world)
-    finally:
-        dist.destroy_process_group()
+    from tests.slab_launch import run_modes
+    run_modes({"stress": stress_mode})

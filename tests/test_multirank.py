@@ -9,27 +9,13 @@ import sys
 import numpy as np
 import pytest
 
+from tests.slab_launch import free_port, launch
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def _launch(mode, nproc=2, timeout=600, extra=(), env_extra=None):
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="2", HSA_ENABLE_IPC_MODE_LEGACY="0", **(env_extra or {}))
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nproc),
-           "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(ROOT, "tests", "mp_gloo_worker.py"), mode] + [str(v) for v in extra]
-    r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=timeout)
-    assert r.returncode == 0, r.stdout[-3000:] + "\n" + r.stderr[-3000:]
-    for k in range(nproc):
-        assert "rank %d %s OK" % (k, mode) in r.stdout, r.stdout[-2000:]
-    return r.stdout
+    return launch("mp_gloo_worker.py", mode, nproc, extra, timeout, env_extra)
 
 
 def test_partition_logic():
@@ -112,7 +98,7 @@ def test_too_thin_slabs_are_refused_on_every_rank():
     rank-dependent failure later would leave the others waiting in a collective)"""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="2", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "tests", "mp_gloo_worker.py"), "gpu", "16", "8", "8", "2"]
+           "--master-port", str(free_port()), os.path.join(ROOT, "tests", "mp_gloo_worker.py"), "gpu", "16", "8", "8", "2"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=180)
     assert r.returncode != 0
     assert (r.stdout + r.stderr).count("too few for 2 multigrid levels on slabs") == 4

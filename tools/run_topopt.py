@@ -16,76 +16,46 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import topopt_in_petsc_amd as tp
 
 
-def _loadcases(argv):
-    """takes every `--loadcase name[:weight]` / `--loadcase=name[:weight]` out of argv -> [(name, weight)]"""
-    cases, rest, i = [], [], 0
-    while i < len(argv):
-        a = argv[i]
-        if a == "--loadcase" or a.startswith("--loadcase="):
-            if a == "--loadcase":
-                i += 1
-                if i >= len(argv):
-                    sys.exit("--loadcase needs a value: top[:weight]")
-            v = argv[i] if a == "--loadcase" else a.split("=", 1)[1]
-            name, _, wt = v.partition(":")
-            if name != "top":
-                sys.exit("--loadcase: the only built-in further load case is 'top', got %r" % name)
-            cases.append((name, float(wt) if wt else 1.0))
-        else:
-            rest.append(a)
-        i += 1
-    return cases, rest
-
-
-def _number_option(argv, name):
-    """takes `name value` / `name=value` out of argv -> (float | None, the rest)"""
-    val, rest, i = None, [], 0
+def _option(name, needs=""):
+    """takes every `name value` / `name=value` out of sys.argv -> the values in order (strings)"""
+    vals, rest, i, argv = [], [], 0, sys.argv[1:]
     while i < len(argv):
         a = argv[i]
         if a == name or a.startswith(name + "="):
             if a == name:
                 i += 1
                 if i >= len(argv):
-                    sys.exit("%s needs a value" % name)
-            val = float(argv[i] if a == name else a.split("=", 1)[1])
+                    sys.exit("%s needs a value%s" % (name, needs))
+            vals.append(argv[i] if a == name else a.split("=", 1)[1])
         else:
             rest.append(a)
         i += 1
-    return val, rest
+    sys.argv[1:] = rest
+    return vals
 
 
-loadcases, sys.argv[1:] = _loadcases(sys.argv[1:])
-stress_limit, sys.argv[1:] = _number_option(sys.argv[1:], "--stress-limit")
-stress_p, sys.argv[1:] = _number_option(sys.argv[1:], "--stress-p")
-stress_q, sys.argv[1:] = _number_option(sys.argv[1:], "--stress-q")
+def _last(name, conv=str):
+    vals = [conv(v) for v in _option(name)]
+    return vals[-1] if vals else None
+
+
+loadcases = []
+for v in _option("--loadcase", ": top[:weight]"):
+    name, _, wt = v.partition(":")
+    if name != "top":
+        sys.exit("--loadcase: the only built-in further load case is 'top', got %r" % name)
+    loadcases.append((name, float(wt) if wt else 1.0))
+stress_limit, stress_p, stress_q = _last("--stress-limit", float), _last("--stress-p", float), _last("--stress-q", float)
 stress = {} if stress_limit is None else dict(stress_limit=stress_limit, stress_P=8.0 if stress_p is None else stress_p,
                                               stress_q=0.5 if stress_q is None else stress_q)
-def _text_option(argv, name):
-    """takes `name value` / `name=value` out of argv -> (str | None, the rest)"""
-    val, rest, i = None, [], 0
-    while i < len(argv):
-        a = argv[i]
-        if a == name or a.startswith(name + "="):
-            if a == name:
-                i += 1
-                if i >= len(argv):
-                    sys.exit("%s needs a value" % name)
-            val = argv[i] if a == name else a.split("=", 1)[1]
-        else:
-            rest.append(a)
-        i += 1
-    return val, rest
-
-
-local_volume, sys.argv[1:] = _text_option(sys.argv[1:], "--local-volume")
+local_volume = _last("--local-volume")
 local = {}
 if local_volume is not None:
     alpha, sep, radius = local_volume.partition(":")
     if not sep:
         sys.exit("--local-volume needs ALPHA:R, got %r" % local_volume)
     local = dict(local_volume=float(alpha), local_volume_R=float(radius))
-overhang, sys.argv[1:] = _text_option(sys.argv[1:], "--overhang")
-self_weight, sys.argv[1:] = _text_option(sys.argv[1:], "--self-weight")
+overhang, self_weight = _last("--overhang"), _last("--self-weight")
 no_point_load = "--no-point-load" in sys.argv[1:]
 sys.argv[1:] = [a for a in sys.argv[1:] if a != "--no-point-load"]
 body = {}

@@ -465,32 +465,32 @@ class LinearElasticity:
     def KSPSolve(self, hist_cap=0, case=0, rhs=None):
         """solve load case `case` on the last assembly, warm-started from that case's own state (rhs: another right-hand side
         than the case's fixed load)"""
-        import numpy as np
-        RHS, U = self._case_rhs[case] if rhs is None else rhs, self._case_U[case]
-        its, rn, bn = C.c_int(), C.c_double(), C.c_double()
-        hist = np.zeros(max(hist_cap, 1))
         import time
         t0 = time.perf_counter()   # the solve ends with a host read of ||r||: wall time == device time
+        rc, its, rn, bn, hist = self._solve(self._case_rhs[case] if rhs is None else rhs, self._case_U[case], hist_cap)
+        self.last_solve_s = time.perf_counter() - t0
+        self.last_its, self.last_rnorm, self.last_bnorm = its, rn, bn
+        self.last_hist = hist[: min(its + 1, hist_cap)] if hist_cap else None
+        self.case_its[case], self.case_rnorm[case], self.case_bnorm[case] = its, rn, bn
+        _chk(rc, "tp_elasticity_solve")
+        return its
+
+    def _solve(self, RHS, U, hist_cap=0):
+        """tp_elasticity_solve on the last assembly -> (rc, its, rnorm, bnorm, hist); records nothing, the caller checks rc"""
+        import numpy as np
+        its, rn, bn = C.c_int(), C.c_double(), C.c_double()
+        hist = np.zeros(max(hist_cap, 1))
         rc = self.L.tp_elasticity_solve(self.handle, _ptr(RHS), _ptr(U), C.byref(its), C.byref(rn),
                                         C.byref(bn), hist.ctypes.data if hist_cap else None, hist_cap)
-        self.last_solve_s = time.perf_counter() - t0
-        self.last_its, self.last_rnorm, self.last_bnorm = its.value, rn.value, bn.value
-        self.last_hist = hist[: min(its.value + 1, hist_cap)] if hist_cap else None
-        self.case_its[case], self.case_rnorm[case], self.case_bnorm[case] = its.value, rn.value, bn.value
-        _chk(rc, "tp_elasticity_solve")
-        return its.value
+        return rc, its.value, rn.value, bn.value, hist
 
     def SolveState(self, xPhys, Emin, Emax, penal, hist_cap=0):
         """LinearElasticity.cc:182-223; several load cases: one assembly, then every case in index order"""
         self.AssembleStiffnessMatrix(xPhys, Emin, Emax, penal)
         if self.body_force is not None:
             self._form_totals(xPhys)
-            for case in range(self.ncases):
-                its = self.KSPSolve(hist_cap, case, rhs=self._case_total[case])
-            return its
-        its = self.KSPSolve(hist_cap)
-        for case in range(1, self.ncases):
-            its = self.KSPSolve(hist_cap, case)
+        for case in range(self.ncases):
+            its = self.KSPSolve(hist_cap, case, rhs=self._case_total[case] if self.body_force is not None else None)
         return its
 
     def Response(self, U_list, V_list, w, xPhys, Emin, Emax, penal, volfrac, dfdx=None, dgdx=None, sums=True):
@@ -536,21 +536,19 @@ class LinearElasticity:
             self._stress_dpdx = self.grid.elem_vec()
         U = self._case_U[case]
         pn, mx = self.Stress(xPhys, Emax, q, P, U=U, dpdx=self._stress_dpdx, adj_rhs=self._stress_rhs)
-        its, rn, bn = C.c_int(), C.c_double(), C.c_double()
         if pn == 0.0:   # no stress anywhere: a zero load, whose solution is lam = 0 -- no solve
             self.lam.zero_()
             self.adjoint_its, self.adjoint_rnorm, self.adjoint_bnorm = 0, 0.0, 0.0
             dsdx.zero_()
             return pn, mx, 0
-        rc = self.L.tp_elasticity_solve(self.handle, _ptr(self._stress_rhs), _ptr(self.lam), C.byref(its), C.byref(rn),
-                                        C.byref(bn), None, 0)
-        self.adjoint_its, self.adjoint_rnorm, self.adjoint_bnorm = its.value, rn.value, bn.value
+        rc, its, self.adjoint_rnorm, self.adjoint_bnorm, _ = self._solve(self._stress_rhs, self.lam)
+        self.adjoint_its = its
         _chk(rc, "tp_elasticity_solve (adjoint)")
         self.Response([U], [self.lam], None, xPhys, Emin, Emax, penal, 0.0, dfdx=dsdx, sums=False)
         if self.body_force is not None:   # d pnorm/dx = dpdx - lam^T (dK/dx u - df/dx)
             self.BodySensitivity([self.lam], None, xPhys, 1.0, dsdx)
         _chk(self.L.tp_vec_axpby(self.grid.handle, _ptr(dsdx), 1.0, _ptr(self._stress_dpdx), 1.0, dsdx.numel()), "tp_vec_axpby")
-        return pn, mx, its.value
+        return pn, mx, its
 
     def Objective(self, xPhys, Emin, Emax, penal, volfrac, dfdx=None, dgdx=None):
         fx, gx = C.c_double(), C.c_double()
@@ -559,49 +557,43 @@ class LinearElasticity:
              "tp_elasticity_objective")
         return fx.value, gx.value
 
-    def ComputeObjectiveConstraintsSensitivities(self, dfdx, dgdx, xPhys, Emin, Emax, penal, volfrac, hist_cap=0):
-        """LinearElasticity.cc:363-445 -> (fx, gx); several load cases: fx = sum_l w_l u_l^T K u_l (last_f_case: the f_l)"""
-        self.SolveState(xPhys, Emin, Emax, penal, hist_cap)
-        if self.body_force is not None:   # u^T K u = (F + f)^T u as it stands; dfdx gains 2 d(u^T N f)/dx per case
-            if self.ncases > 1:
-                fx, gx, self.last_f_case = self.Response(self._case_U, None, self.case_weight, xPhys, Emin, Emax, penal, volfrac,
-                                                         dfdx, dgdx)
-            else:
-                fx, gx = self.Objective(xPhys, Emin, Emax, penal, volfrac, dfdx, dgdx)
-            self.BodySensitivity(self._case_U, self.case_weight, xPhys, 2.0, dfdx)
-            return fx, gx
+    def _evaluate(self, dfdx, dgdx, sums, xPhys, Emin, Emax, penal, volfrac):
+        """objective and sensitivities of the current states -> (fx, gx), (None, None) without sums: one case through the
+        reference's three single-case entry points, several through Response (last_f_case: the f_l)"""
         if self.ncases > 1:
-            fx, gx, self.last_f_case = self.Response(self._case_U, None, self.case_weight, xPhys, Emin, Emax, penal, volfrac,
-                                                     dfdx, dgdx)
+            fx, gx, f_case = self.Response(self._case_U, None, self.case_weight, xPhys, Emin, Emax, penal, volfrac, dfdx, dgdx, sums)
+            if sums:
+                self.last_f_case = f_case
             return fx, gx
-        return self.Objective(xPhys, Emin, Emax, penal, volfrac, dfdx, dgdx)
-
-    def ComputeObjectiveConstraints(self, xPhys, Emin, Emax, penal, volfrac, hist_cap=0):
-        """LinearElasticity.cc:225-297: solve, then fx and gx -- no sensitivities -> (fx, gx)"""
-        self.SolveState(xPhys, Emin, Emax, penal, hist_cap)
-        if self.ncases > 1:
-            fx, gx, self.last_f_case = self.Response(self._case_U, None, self.case_weight, xPhys, Emin, Emax, penal, volfrac)
-            return fx, gx
+        if not sums:
+            _chk(self.L.tp_elasticity_sensitivities(self.handle, _ptr(self.U), _ptr(xPhys), Emin, Emax, penal, _ptr(dfdx),
+                                                    _ptr(dgdx)), "tp_elasticity_sensitivities")
+            return None, None
+        if dfdx is not None or dgdx is not None:
+            return self.Objective(xPhys, Emin, Emax, penal, volfrac, dfdx, dgdx)
         fx, gx = C.c_double(), C.c_double()
         _chk(self.L.tp_elasticity_objective_only(self.handle, _ptr(self.U), _ptr(xPhys), Emin, Emax, penal, volfrac,
                                                  C.byref(fx), C.byref(gx)), "tp_elasticity_objective_only")
         return fx.value, gx.value
 
+    def ComputeObjectiveConstraintsSensitivities(self, dfdx, dgdx, xPhys, Emin, Emax, penal, volfrac, hist_cap=0):
+        """LinearElasticity.cc:363-445 -> (fx, gx); several load cases: fx = sum_l w_l u_l^T K u_l (last_f_case: the f_l)"""
+        self.SolveState(xPhys, Emin, Emax, penal, hist_cap)
+        fx, gx = self._evaluate(dfdx, dgdx, True, xPhys, Emin, Emax, penal, volfrac)
+        if self.body_force is not None:   # u^T K u = (F + f)^T u as it stands; dfdx gains 2 d(u^T N f)/dx per case
+            self.BodySensitivity(self._case_U, self.case_weight, xPhys, 2.0, dfdx)
+        return fx, gx
+
+    def ComputeObjectiveConstraints(self, xPhys, Emin, Emax, penal, volfrac, hist_cap=0):
+        """LinearElasticity.cc:225-297: solve, then fx and gx -- no sensitivities -> (fx, gx)"""
+        self.SolveState(xPhys, Emin, Emax, penal, hist_cap)
+        return self._evaluate(None, None, True, xPhys, Emin, Emax, penal, volfrac)
+
     def ComputeSensitivities(self, dfdx, dgdx, xPhys, Emin, Emax, penal, volfrac=0.0):
         """LinearElasticity.cc:299-361: dfdx, dgdx of the current state U (no solve); several load cases: of all states"""
+        self._evaluate(dfdx, dgdx, False, xPhys, Emin, Emax, penal, volfrac)
         if self.body_force is not None:
-            if self.ncases > 1:
-                self.Response(self._case_U, None, self.case_weight, xPhys, Emin, Emax, penal, volfrac, dfdx, dgdx, sums=False)
-            else:
-                _chk(self.L.tp_elasticity_sensitivities(self.handle, _ptr(self.U), _ptr(xPhys), Emin, Emax, penal, _ptr(dfdx),
-                                                        _ptr(dgdx) if dgdx is not None else None), "tp_elasticity_sensitivities")
             self.BodySensitivity(self._case_U, self.case_weight, xPhys, 2.0, dfdx)
-            return
-        if self.ncases > 1:
-            self.Response(self._case_U, None, self.case_weight, xPhys, Emin, Emax, penal, volfrac, dfdx, dgdx, sums=False)
-            return
-        _chk(self.L.tp_elasticity_sensitivities(self.handle, _ptr(self.U), _ptr(xPhys), Emin, Emax, penal, _ptr(dfdx),
-                                                _ptr(dgdx) if dgdx is not None else None), "tp_elasticity_sensitivities")
 
     # ---- introspection used by the parity tests ----------------------------
     def petsc_options(self):

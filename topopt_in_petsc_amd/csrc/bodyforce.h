@@ -1,6 +1,6 @@
 // bodyforce.h -- self-weight: a design-dependent body force b (per unit volume at full density) on the trilinear hex, its
 // consistent nodal load and the term it adds to the sensitivity of any linear response of the state.  Included from
-// topopt_amd.hip behind the elasticity entry points.  DESIGN.md 4.12.
+// topopt_amd.hip behind stress.h.  DESIGN.md 4.12.
 //
 // V_e = hx hy hz, x_e the physical density the responses are evaluated on.
 // Mass interpolation (the form of Du & Olhoff, "Topological design of freely vibrating continuum structures for maximum values
@@ -77,25 +77,19 @@ __global__ __launch_bounds__(BLK) void k_body_sens(Geom g, BodyPar p, BodyFields
                                                    const double *__restrict__ x, double scale, double *__restrict__ dfdx) {
     const long t = blockIdx.x * (long)BLK + threadIdx.x;
     if (t >= g.own_elems()) return;
-    const int i = (int)(t % g.ex), j = (int)((t / g.ex) % g.ey), k = (int)(t / ((long)g.ex * g.ey));
-    const long nd0 = (long)i + (long)g.nx * (j + (long)g.ny * k);
+    int i, j, k;
+    elem_ijk(g, t, i, j, k);
+    const long nd0 = elem_node0(g, i, j, k);
     double bn[24];
+    gather24(g, nd0, N, bn);
 #pragma unroll
-    for (int c8 = 0; c8 < 8; c8++) {
-        const long nd = nd0 + LXc(c8) + (long)g.nx * (LYc(c8) + (long)g.ny * LZc(c8));
-#pragma unroll
-        for (int c = 0; c < 3; c++) bn[3 * c8 + c] = p.vb[c] * N[3 * nd + c];
-    }
+    for (int r = 0; r < 24; r++) bn[r] = p.vb[r % 3] * bn[r];
     double acc = 0.0;
     for (int l = 0; l < a.ncase; l++) {
-        const double *__restrict__ V = a.V[l];
-        double s = 0.0;
+        double ve[24], s = 0.0;
+        gather24(g, nd0, a.V[l], ve);
 #pragma unroll
-        for (int c8 = 0; c8 < 8; c8++) {
-            const long nd = nd0 + LXc(c8) + (long)g.nx * (LYc(c8) + (long)g.ny * LZc(c8));
-#pragma unroll
-            for (int c = 0; c < 3; c++) s = fma(bn[3 * c8 + c], V[3 * nd + c], s);
-        }
+        for (int r = 0; r < 24; r++) s = fma(bn[r], ve[r], s);
         acc = fma(a.w[l], s, acc);
     }
     dfdx[t] += (scale * body_dmass(x[t], p.x_low, p.inv_low)) * acc;

@@ -81,6 +81,36 @@ __host__ __device__ constexpr int LZc(int a) { return a >= 4 ? 1 : 0; }
 __host__ __device__ constexpr int corner_of(int lx, int ly, int lz) {
     return lz * 4 + (ly ? (lx ? 2 : 3) : (lx ? 1 : 0));
 }
+// The element prologue of the one-thread-per-element kernels: own element t -> (i, j, k); node (i, j, k), which is corner 0 of
+// element (i, j, k); corner a of that element, from (i, j, k) or from the corner-0 node (kernels that keep one index live over
+// a loop of fields); the 24 values of a 3-dof field on the 8 corners, either way.  Geom by value: nothing but index arithmetic
+// is left after inlining, and the kernels keep the registers they had with the expressions written out.
+__device__ __forceinline__ void elem_ijk(const Geom g, long t, int &i, int &j, int &k) {
+    i = (int)(t % g.ex), j = (int)((t / g.ex) % g.ey), k = (int)(t / ((long)g.ex * g.ey));
+}
+__device__ __forceinline__ long elem_node0(const Geom g, int i, int j, int k) { return (long)i + (long)g.nx * (j + (long)g.ny * k); }
+__device__ __forceinline__ long corner_node(const Geom g, int i, int j, int k, int a) {
+    return (long)(i + LXc(a)) + (long)g.nx * ((j + LYc(a)) + (long)g.ny * (k + LZc(a)));
+}
+__device__ __forceinline__ long corner_node(const Geom g, long nd0, int a) {
+    return nd0 + LXc(a) + (long)g.nx * (LYc(a) + (long)g.ny * LZc(a));
+}
+__device__ __forceinline__ void gather24(const Geom g, int i, int j, int k, const double *__restrict__ U, double (&ue)[24]) {
+#pragma unroll
+    for (int a = 0; a < 8; a++) {
+        const long nd = corner_node(g, i, j, k, a);
+#pragma unroll
+        for (int c = 0; c < 3; c++) ue[3 * a + c] = U[3 * nd + c];
+    }
+}
+__device__ __forceinline__ void gather24(const Geom g, long nd0, const double *__restrict__ U, double (&ue)[24]) {
+#pragma unroll
+    for (int a = 0; a < 8; a++) {
+        const long nd = corner_node(g, nd0, a);
+#pragma unroll
+        for (int c = 0; c < 3; c++) ue[3 * a + c] = U[3 * nd + c];
+    }
+}
 
 // ---------------------------------------------------------------------------
 // deterministic reductions: wave shuffle -> LDS -> one partial per workgroup,
@@ -218,6 +248,27 @@ __global__ __launch_bounds__(BLK) void k_reduce_final_n(const double *__restrict
         for (int b = threadIdx.x; b < nblocks; b += BLK) s += partials[(long)v * nblocks + b];
         s = block_sum(s);
         if (threadIdx.x == 0) out[v] = s;
+    }
+}
+// out[0] = max_b partials[b]; and out[0] = sum_b partials[b] (the order above), out[1] = max_b partials[nblocks + b].  Maxima of
+// non-negative values (stress.h, mma.h).
+__global__ __launch_bounds__(BLK) void k_max_final(const double *__restrict__ partials, int nblocks, double *__restrict__ out) {
+    double m = 0.0;
+    for (int b = threadIdx.x; b < nblocks; b += BLK) m = fmax(m, partials[b]);
+    m = block_max(m);
+    if (threadIdx.x == 0) out[0] = m;
+}
+__global__ __launch_bounds__(BLK) void k_sum_max_final(const double *__restrict__ partials, int nblocks, double *__restrict__ out) {
+    double s = 0.0, m = 0.0;
+    for (int b = threadIdx.x; b < nblocks; b += BLK) {
+        s += partials[b];
+        m = fmax(m, partials[nblocks + b]);
+    }
+    s = block_sum(s);
+    m = block_max(m);
+    if (threadIdx.x == 0) {
+        out[0] = s;
+        out[1] = m;
     }
 }
 

@@ -176,6 +176,33 @@ inline int read_scal_end(tp_grid *g, int n, double *out) {
     return TP_OK;
 }
 
+// Values of all ranks side by side on every rank, through the sum hook: each of the `total` slots belongs to one rank, which
+// puts its value there while the others add 0 (exact); 16 slots -- the hook's buffer -- at a time.  This rank owns the slots
+// [my0, my0 + myn) and gives myv; out[total] is a host array.  Blocking, uses g->h_scal, not timed (no CommMark).  Collective.
+static int gather_slots(tp_grid *g, int total, int my0, int myn, const double *myv, double *out) {
+    for (int o = 0; o < total; o += 16) {
+        const int cnt = total - o < 16 ? total - o : 16;
+        double slots[16] = {0};
+        for (int s = 0; s < myn; s++)
+            if (my0 + s >= o && my0 + s < o + cnt) slots[my0 + s - o] = myv[s];
+        TP_HIP(hipMemcpyAsync(g->comm.red, slots, sizeof(double) * cnt, hipMemcpyHostToDevice, g->stream));
+        TP_HIP(hipStreamSynchronize(g->stream));  // `slots` is a stack buffer
+        if (g->comm.allreduce_sum(g->comm.user, cnt)) return TP_ERR_COMM;
+        TP_HIP(hipMemcpyAsync(g->h_scal, g->comm.red, sizeof(double) * cnt, hipMemcpyDeviceToHost, g->stream));
+        TP_HIP(hipStreamSynchronize(g->stream));
+        for (int s = 0; s < cnt; s++) out[o + s] = g->h_scal[s];
+    }
+    return TP_OK;
+}
+// *v <- its maximum over the ranks (one slot per rank; fmax: a NaN of another rank is dropped).  One rank: nothing, no hook.
+static int rank_max(tp_grid *g, double *v) {
+    if (!g->has_comm) return TP_OK;
+    std::vector<double> all((size_t)g->nranks);
+    TP_TRY(gather_slots(g, g->nranks, g->rank, 1, v, all.data()));
+    for (double a : all) *v = fmax(*v, a);
+    return TP_OK;
+}
+
 inline int dot_to_slot(tp_grid *g, const double *a, const double *b, long n, int slot) {
     int nb = grid_for(n, 2048);
     TP_LAUNCH(k_dot, dim3(nb), dim3(BLK), 0, g->stream, a, b, n, g->partials, tail_ticket(g), g->scal + slot);

@@ -167,37 +167,16 @@ extern "C" int tp_localvol_constraint(tp_localvol *lv, const double *xPhys, doub
         S = g->h_scal[0];
         mx = g->h_scal[1];
     } else {
-        // Layer sums of all ranks through the sum hook, every layer in its own slot (x + 0 is exact), 16 slots at a time; then
-        // S in ascending global z -- the order k_localvol_reduce has on one rank.  The maximum: one slot per rank (as
-        // tp_elasticity_stress).
-        std::vector<double> mine((size_t)(2 + nl));
+        // Layer sums of all ranks side by side (grid.h: gather_slots; x + 0 is exact), then S in ascending global z -- the order
+        // k_localvol_reduce has on one rank.  The maximum: rank_max.
+        std::vector<double> mine((size_t)(2 + nl)), layer((size_t)g->ez_glob);
         TP_HIP(hipMemcpyAsync(mine.data(), lv->red, sizeof(double) * mine.size(), hipMemcpyDeviceToHost, g->stream));
         TP_HIP(hipStreamSynchronize(g->stream));
-        auto gather16 = [&](int o, int cnt, int my0, int myn, const double *myv, double *res) -> int {
-            double slots[16] = {0};
-            for (int s = 0; s < myn; s++)
-                if (my0 + s >= o && my0 + s < o + cnt) slots[my0 + s - o] = myv[s];
-            TP_HIP(hipMemcpyAsync(g->comm.red, slots, sizeof(double) * cnt, hipMemcpyHostToDevice, g->stream));
-            TP_HIP(hipStreamSynchronize(g->stream));  // `slots` is a stack buffer
-            if (g->comm.allreduce_sum(g->comm.user, cnt)) return TP_ERR_COMM;
-            TP_HIP(hipMemcpyAsync(g->h_scal, g->comm.red, sizeof(double) * cnt, hipMemcpyDeviceToHost, g->stream));
-            TP_HIP(hipStreamSynchronize(g->stream));
-            for (int s = 0; s < cnt; s++) res[s] = g->h_scal[s];
-            return TP_OK;
-        };
+        TP_TRY(gather_slots(g, g->ez_glob, g->rank * nl, nl, mine.data() + 2, layer.data()));
         S = 0.0;
-        mx = 0.0;
-        double res[16];
-        for (int o = 0; o < g->ez_glob; o += 16) {
-            const int cnt = g->ez_glob - o < 16 ? g->ez_glob - o : 16;
-            TP_TRY(gather16(o, cnt, g->rank * nl, nl, mine.data() + 2, res));
-            for (int s = 0; s < cnt; s++) S += res[s];
-        }
-        for (int o = 0; o < g->nranks; o += 16) {
-            const int cnt = g->nranks - o < 16 ? g->nranks - o : 16;
-            TP_TRY(gather16(o, cnt, g->rank, 1, mine.data() + 1, res));
-            for (int s = 0; s < cnt; s++) mx = fmax(mx, res[s]);
-        }
+        for (double s : layer) S += s;
+        mx = mine[1];
+        TP_TRY(rank_max(g, &mx));
     }
     const double n = (double)((long)g->ex * g->ey * g->ez_glob);
     const double pn = S != 0.0 ? pow(S / n, 1.0 / p) : 0.0;

@@ -159,42 +159,23 @@ __global__ __launch_bounds__(BLK) void k_mma_movelimit(long n, double Xmin, doub
 // partial max |x - xold|, then xold <- x
 __global__ __launch_bounds__(BLK) void k_mma_change(long n, const double *__restrict__ x, double *__restrict__ xold,
                                                     double *__restrict__ partials) {
-    __shared__ double s_m[BLK];
     double ch = 0.0;
     for (long i = blockIdx.x * (long)BLK + threadIdx.x; i < n; i += (long)gridDim.x * BLK) {
         ch = fmax(ch, fabs(x[i] - xold[i]));
         xold[i] = x[i];
     }
-    s_m[threadIdx.x] = ch;
-    __syncthreads();
-    for (int o = BLK / 2; o > 0; o >>= 1) {
-        if (threadIdx.x < o) s_m[threadIdx.x] = fmax(s_m[threadIdx.x], s_m[threadIdx.x + o]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partials[blockIdx.x] = s_m[0];
-}
-__global__ __launch_bounds__(BLK) void k_max_final(const double *__restrict__ partials, int nb, double *__restrict__ out) {
-    __shared__ double s_m[BLK];
-    double v = 0.0;
-    for (int b = threadIdx.x; b < nb; b += BLK) v = fmax(v, partials[b]);
-    s_m[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = BLK / 2; o > 0; o >>= 1) {
-        if (threadIdx.x < o) s_m[threadIdx.x] = fmax(s_m[threadIdx.x], s_m[threadIdx.x + o]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = s_m[0];
+    ch = block_max(ch);
+    if (threadIdx.x == 0) partials[blockIdx.x] = ch;
 }
 
 // KKTresidual (MMA.cc:452-474): per element ri = dfdx + sum_j lam_j dgdx_j (left to right), the bound multipliers
 // with their 1e-5 tolerances, and the three squared terms.  partials[b] = the workgroup's sum (block_sum),
-// partials[nb + b] = its max; k_sum_max_final finishes both.
+// partials[nb + b] = its max; k_sum_max_final (common.h) finishes both.
 __global__ __launch_bounds__(BLK) void k_mma_kkt(long n, int m, MmaLam lm, const double *__restrict__ x,
                                                  const double *__restrict__ xmin, const double *__restrict__ xmax,
                                                  const double *__restrict__ dfdx, const double *const *dgdx,
                                                  double *__restrict__ partials) {
 #pragma clang fp contract(off)
-    __shared__ double s_m[BLK];
     double s = 0.0, mx = 0.0;
     for (long i = blockIdx.x * (long)BLK + threadIdx.x; i < n; i += (long)gridDim.x * BLK) {
         const double xv = x[i], lo = xmin[i], hi = xmax[i];
@@ -214,35 +195,10 @@ __global__ __launch_bounds__(BLK) void k_mma_kkt(long n, int m, MmaLam lm, const
         mx = fmax(fabs(resi), mx);
     }
     const double t = block_sum(s);
-    s_m[threadIdx.x] = mx;
-    __syncthreads();
-    for (int o = BLK / 2; o > 0; o >>= 1) {
-        if (threadIdx.x < o) s_m[threadIdx.x] = fmax(s_m[threadIdx.x], s_m[threadIdx.x + o]);
-        __syncthreads();
-    }
+    mx = block_max(mx);
     if (threadIdx.x == 0) {
         partials[blockIdx.x] = t;
-        partials[gridDim.x + blockIdx.x] = s_m[0];
-    }
-}
-// out[0] = sum_b partials[b] (k_reduce_multi's order), out[1] = max_b partials[nb + b]
-__global__ __launch_bounds__(BLK) void k_sum_max_final(const double *__restrict__ partials, int nb, double *__restrict__ out) {
-    __shared__ double s_m[BLK];
-    double s = 0.0, v = 0.0;
-    for (int b = threadIdx.x; b < nb; b += BLK) {
-        s += partials[b];
-        v = fmax(v, partials[nb + b]);
-    }
-    s = block_sum(s);
-    s_m[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = BLK / 2; o > 0; o >>= 1) {
-        if (threadIdx.x < o) s_m[threadIdx.x] = fmax(s_m[threadIdx.x], s_m[threadIdx.x + o]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        out[0] = s;
-        out[1] = s_m[0];
+        partials[gridDim.x + blockIdx.x] = mx;
     }
 }
 
@@ -339,21 +295,7 @@ extern "C" int tp_mma_design_change(tp_mma *M, const double *x, double *xold, do
     TP_HIP(hipMemcpyAsync(g->h_scal, M->red, sizeof(double), hipMemcpyDeviceToHost, g->stream));
     TP_HIP(hipStreamSynchronize(g->stream));
     double v = g->h_scal[0];
-    if (g->has_comm) {
-        // max over ranks through the sum hook: every rank's value in its own slot, 16 slots (the hook's buffer) at a time
-        const double mine = v;
-        for (int o = 0; o < g->nranks; o += 16) {
-            const int cnt = g->nranks - o < 16 ? g->nranks - o : 16;
-            double slots[16] = {0};
-            if (g->rank >= o && g->rank < o + cnt) slots[g->rank - o] = mine;
-            TP_HIP(hipMemcpyAsync(g->comm.red, slots, sizeof(double) * cnt, hipMemcpyHostToDevice, g->stream));
-            TP_HIP(hipStreamSynchronize(g->stream));  // `slots` is a stack buffer
-            if (g->comm.allreduce_sum(g->comm.user, cnt)) return TP_ERR_COMM;
-            TP_HIP(hipMemcpyAsync(g->h_scal, g->comm.red, sizeof(double) * cnt, hipMemcpyDeviceToHost, g->stream));
-            TP_HIP(hipStreamSynchronize(g->stream));
-            for (int r = 0; r < cnt; r++) v = fmax(v, g->h_scal[r]);
-        }
-    }
+    TP_TRY(rank_max(g, &v));
     *ch = v;
     return TP_OK;
 }
@@ -547,8 +489,8 @@ extern "C" int tp_mma_constraint_modification(tp_mma *M, int on) {
     return TP_OK;
 }
 // KKTresidual (MMA.cc:428-496): the element pass on the device (k_mma_kkt + k_sum_max_final), the sum over ranks
-// through the comm hook, the max over ranks through one slot per rank (as tp_mma_design_change), then the scalar
-// term of the constraints and the square root on the host in the reference's order (:487-493).
+// through the comm hook, the max over ranks (grid.h: rank_max), then the scalar term of the constraints and the square
+// root on the host in the reference's order (:487-493).
 extern "C" int tp_mma_kkt_residual(tp_mma *M, const double *x, const double *dfdx, const double *gx,
                                    const double *const *dgdx, const double *xmin, const double *xmax, double *norm2,
                                    double *normInf) {
@@ -575,20 +517,7 @@ extern "C" int tp_mma_kkt_residual(tp_mma *M, const double *x, const double *dfd
     TP_HIP(hipStreamSynchronize(s));
     n2 = g->h_scal[0];
     nI = g->h_scal[1];
-    if (g->has_comm) {
-        const double mine = nI;
-        for (int o = 0; o < g->nranks; o += 16) {
-            const int cnt = g->nranks - o < 16 ? g->nranks - o : 16;
-            double slots[16] = {0};
-            if (g->rank >= o && g->rank < o + cnt) slots[g->rank - o] = mine;
-            TP_HIP(hipMemcpyAsync(g->comm.red, slots, sizeof(double) * cnt, hipMemcpyHostToDevice, s));
-            TP_HIP(hipStreamSynchronize(s));  // `slots` is a stack buffer
-            if (g->comm.allreduce_sum(g->comm.user, cnt)) return TP_ERR_COMM;
-            TP_HIP(hipMemcpyAsync(g->h_scal, g->comm.red, sizeof(double) * cnt, hipMemcpyDeviceToHost, s));
-            TP_HIP(hipStreamSynchronize(s));
-            for (int r = 0; r < cnt; r++) nI = fmax(nI, g->h_scal[r]);
-        }
-    }
+    TP_TRY(rank_max(g, &nI));
     double ri = 0.0;
     for (int j = 0; j < m; j++) ri += M->lam[j] * (M->a[j] * M->z + M->y[j] - gx[j]);
     n2 += pow(ri, 2.0);

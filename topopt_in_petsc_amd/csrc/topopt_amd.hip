@@ -1235,415 +1235,6 @@ extern "C" int tp_elasticity_solve(tp_elasticity *e, const double *RHS, double *
     return rc;
 }
 
-// fx = sum_e E_e u_e^T KE u_e, dfdx_e = -p x^(p-1) (Emax-Emin) u_e^T KE u_e, partial sum x
-// (LinearElasticity.cc:405-437); one thread per own element, KE rows wave-uniform.
-// REDUCE = false: the sensitivities alone (LinearElasticity.cc:299-361) -- no sums, nothing for the host to wait for.
-template <bool REDUCE>
-__global__ __launch_bounds__(BLK) void k_objective(Geom g, const double *__restrict__ KE, const double *__restrict__ U,
-                                                   const double *__restrict__ x, double Emin, double Emax, double penal,
-                                                   double *__restrict__ dfdx, double *__restrict__ partials) {
-    const long nel = g.own_elems();
-    const long t = blockIdx.x * (long)BLK + threadIdx.x;
-    double f = 0.0, vol = 0.0;
-    if (t < nel) {
-        const int i = (int)(t % g.ex), j = (int)((t / g.ex) % g.ey), k = (int)(t / ((long)g.ex * g.ey));
-        double ue[24];
-#pragma unroll
-        for (int a = 0; a < 8; a++) {
-            const long nd = (long)(i + LXc(a)) + (long)g.nx * ((j + LYc(a)) + (long)g.ny * (k + LZc(a)));
-#pragma unroll
-            for (int c = 0; c < 3; c++) ue[3 * a + c] = U[3 * nd + c];
-        }
-        double uKu = 0.0;
-#pragma unroll
-        for (int r = 0; r < 24; r++) {
-            double s = 0.0;
-#pragma unroll
-            for (int c = 0; c < 24; c++) s = fma(KE[r * 24 + c], ue[c], s);
-            uKu = fma(ue[r], s, uKu);
-        }
-        const double xe = x[t];
-        f = (Emin + pow(xe, penal) * (Emax - Emin)) * uKu;
-        vol = xe;
-        if (dfdx) dfdx[t] = -1.0 * penal * pow(xe, penal - 1) * (Emax - Emin) * uKu;
-    }
-    if (!REDUCE) return;
-    f = block_sum(f);
-    vol = block_sum(vol);
-    if (threadIdx.x == 0) {
-        partials[blockIdx.x] = f;
-        partials[gridDim.x + blockIdx.x] = vol;
-    }
-}
-
-extern "C" int tp_elasticity_objective(tp_elasticity *e, const double *U, const double *xPhys, double Emin, double Emax,
-                                       double penal, double volfrac, double *fx, double *gx, double *dfdx,
-                                       double *dgdx) {
-    tp_grid *g = e->grid;
-    Geom q = e->mg.lv[0].g;
-    const long nel = q.own_elems();
-    const long nel_glob = (long)g->ex * g->ey * g->ez_glob;
-    TP_TRY(halo_nodes(g, q, const_cast<double *>(U), 3));  // DMGlobalToLocal, :388-390
-    const int nb = (int)((nel + BLK - 1) / BLK);
-    if (!fx && !gx) {  // sensitivities only: no reduction, no host synchronisation
-        if (dfdx) {
-            TP_LAUNCH(k_objective<false>, dim3(nb), dim3(BLK), 0, g->stream, q, e->d_KE, U, xPhys, Emin, Emax, penal, dfdx, g->partials);
-            count_launch(g, 24.0 * q.owned_nodes() + 16.0 * nel, 2.0 * 600 * nel);
-        }
-    } else {
-        TP_LAUNCH(k_objective<true>, dim3(nb), dim3(BLK), 0, g->stream, q, e->d_KE, U, xPhys, Emin, Emax, penal, dfdx, g->partials);
-        count_launch(g, 24.0 * q.owned_nodes() + 16.0 * nel, 2.0 * 600 * nel);
-        TP_TRY(reduce_partials<2>(g, nb, S_TMP));
-        double v[2];
-        TP_TRY(read_scal(g, S_TMP, 2, v));
-        if (fx) *fx = v[0];
-        if (gx) *gx = v[1] / (double)nel_glob - volfrac;
-    }
-    if (dgdx) TP_TRY(tp_vec_set(g, dgdx, 1.0 / (double)nel_glob, nel));
-    return TP_OK;
-}
-// The reference's split forms (main.cc can call either pair instead of the fused method):
-// ComputeObjectiveConstraints minus the solve (LinearElasticity.cc:237-294): fx and gx of the state U, no sensitivities
-extern "C" int tp_elasticity_objective_only(tp_elasticity *e, const double *U, const double *xPhys, double Emin, double Emax,
-                                            double penal, double volfrac, double *fx, double *gx) {
-    if (!e || !U || !xPhys || !fx || !gx) return TP_ERR_ARG;
-    return tp_elasticity_objective(e, U, xPhys, Emin, Emax, penal, volfrac, fx, gx, nullptr, nullptr);
-}
-// ComputeSensitivities (LinearElasticity.cc:299-361): dfdx, dgdx of the state U as it is -- no solve, no sums
-extern "C" int tp_elasticity_sensitivities(tp_elasticity *e, const double *U, const double *xPhys, double Emin, double Emax,
-                                           double penal, double *dfdx, double *dgdx) {
-    if (!e || !U || !xPhys || !dfdx) return TP_ERR_ARG;
-    return tp_elasticity_objective(e, U, xPhys, Emin, Emax, penal, 0.0, nullptr, nullptr, dfdx, dgdx);
-}
-
-// ---- several load cases: the weighted response  sum_l w_l sum_e E_e v_l^T KE u_l  and its sensitivity in one pass
-// (V_l = U_l: compliance of case l; V_l an adjoint state: the sensitivity of any linear response of U_l).
-// One thread per own element like k_objective, the cases in a loop inside the thread: xPhys is read once, pow is
-// evaluated once (x^p = x^(p-1) x), dfdx is written once.  The registers hold ONE case's u_e at a time (48 VGPRs); v_e is
-// never held -- entry r is read where row r of KE u_e is complete, and used once.  BILINEAR = false (every V_l is U_l)
-// has no loads of V at all.  REDUCE: ncase + 1 block sums (f_l = sum_e E_e v_l^T KE u_l, unweighted, and the volume) to
-// partials[value][block], same layout and summation order as k_objective's two.
-struct RespArgs {
-    const double *U[TP_MAX_CASES];
-    const double *V[TP_MAX_CASES];  // BILINEAR: never NULL (the host puts U[l] where the caller passed none)
-    double w[TP_MAX_CASES];
-    int ncase;
-};
-template <bool BILINEAR, bool REDUCE>
-__global__ __launch_bounds__(BLK) void k_response(Geom g, const double *__restrict__ KE, RespArgs a,
-                                                  const double *__restrict__ x, double Emin, double Emax, double penal,
-                                                  double *__restrict__ dfdx, double *__restrict__ partials) {
-    const long nel = g.own_elems();
-    const long t = blockIdx.x * (long)BLK + threadIdx.x;
-    const bool in = t < nel;
-    long nd0 = 0;
-    double xe = 0.0, xp1 = 0.0, E = 0.0;
-    if (in) {
-        const int i = (int)(t % g.ex), j = (int)((t / g.ex) % g.ey), k = (int)(t / ((long)g.ex * g.ey));
-        nd0 = (long)i + (long)g.nx * (j + (long)g.ny * k);
-        xe = x[t];
-        xp1 = pow(xe, penal - 1);
-        E = Emin + (xe == 0.0 ? 0.0 : xp1 * xe) * (Emax - Emin);  // (x = 0: x^p = 0 for p > 0 whatever x^(p-1) is)
-    }
-    double acc = 0.0;
-    for (int l = 0; l < a.ncase; l++) {
-        double vKu = 0.0;
-        if (in) {
-            const double *__restrict__ U = a.U[l];
-            double ue[24];
-#pragma unroll
-            for (int c8 = 0; c8 < 8; c8++) {
-                const long nd = nd0 + LXc(c8) + (long)g.nx * (LYc(c8) + (long)g.ny * LZc(c8));
-#pragma unroll
-                for (int c = 0; c < 3; c++) ue[3 * c8 + c] = U[3 * nd + c];
-            }
-            const double *__restrict__ V = BILINEAR ? a.V[l] : nullptr;
-#pragma unroll
-            for (int r = 0; r < 24; r++) {
-                double s = 0.0;
-#pragma unroll
-                for (int c = 0; c < 24; c++) s = fma(KE[r * 24 + c], ue[c], s);
-                double vr = ue[r];
-                if (BILINEAR) {
-                    const long nd = nd0 + LXc(r / 3) + (long)g.nx * (LYc(r / 3) + (long)g.ny * LZc(r / 3));
-                    vr = V[3 * nd + r % 3];
-                }
-                vKu = fma(vr, s, vKu);
-            }
-            acc = fma(a.w[l], vKu, acc);
-        }
-        if (REDUCE) {  // (every thread of the workgroup passes here: l is uniform)
-            const double f = block_sum(E * vKu);
-            if (threadIdx.x == 0) partials[(long)l * gridDim.x + blockIdx.x] = f;
-        }
-    }
-    if (in && dfdx) dfdx[t] = -1.0 * penal * xp1 * (Emax - Emin) * acc;
-    if (REDUCE) {
-        const double vol = block_sum(xe);
-        if (threadIdx.x == 0) partials[(long)a.ncase * gridDim.x + blockIdx.x] = vol;
-    }
-}
-
-extern "C" int tp_elasticity_response(tp_elasticity *e, int ncase, const double *const *U, const double *const *V, const double *w,
-                                      const double *xPhys, double Emin, double Emax, double penal, double volfrac, double *f_case,
-                                      double *fx, double *gx, double *dfdx, double *dgdx) {
-    if (!e || !U || !xPhys || ncase < 1 || ncase > TP_MAX_CASES) return TP_ERR_ARG;
-    for (int l = 0; l < ncase; l++)
-        if (!U[l]) return TP_ERR_ARG;
-    tp_grid *g = e->grid;
-    Geom q = e->mg.lv[0].g;
-    const long nel = q.own_elems();
-    const long nel_glob = (long)g->ex * g->ey * g->ez_glob;
-    RespArgs a{};
-    a.ncase = ncase;
-    bool bilinear = false;
-    const double *distinct[2 * TP_MAX_CASES];
-    int ndistinct = 0;
-    auto note = [&](const double *p) {
-        for (int i = 0; i < ndistinct; i++)
-            if (distinct[i] == p) return;
-        distinct[ndistinct++] = p;
-    };
-    for (int l = 0; l < ncase; l++) {
-        a.U[l] = U[l];
-        a.V[l] = (V && V[l]) ? V[l] : U[l];
-        a.w[l] = w ? w[l] : 1.0;
-        bilinear = bilinear || a.V[l] != a.U[l];
-        note(a.U[l]);
-        note(a.V[l]);
-    }
-    for (int i = 0; i < ndistinct; i++) TP_TRY(halo_nodes(g, q, const_cast<double *>(distinct[i]), 3));  // DMGlobalToLocal, :388-390
-    const int nb = (int)((nel + BLK - 1) / BLK);
-    const double bytes = 24.0 * q.owned_nodes() * ndistinct + 16.0 * nel, flops = 2.0 * 600 * nel * ncase;
-    if (!fx && !gx && !f_case) {  // sensitivities only: no reduction, no host synchronisation
-        if (dfdx) {
-            if (bilinear)
-                TP_LAUNCH((k_response<true, false>), dim3(nb), dim3(BLK), 0, g->stream, q, e->d_KE, a, xPhys, Emin, Emax, penal, dfdx, (double *)nullptr);
-            else
-                TP_LAUNCH((k_response<false, false>), dim3(nb), dim3(BLK), 0, g->stream, q, e->d_KE, a, xPhys, Emin, Emax, penal, dfdx, (double *)nullptr);
-            count_launch(g, bytes, flops);
-        }
-    } else {
-        if (e->resp_nb < nb) {  // (the grid's own partials hold four values per workgroup)
-            TP_HIP(hipStreamSynchronize(g->stream));
-            (void)hipFree(e->d_resp);
-            e->d_resp = nullptr;
-            e->resp_nb = 0;
-            TP_HIP(hipMalloc((void **)&e->d_resp, sizeof(double) * (TP_MAX_CASES + 1) * (size_t)nb));
-            e->resp_nb = nb;
-        }
-        if (bilinear)
-            TP_LAUNCH((k_response<true, true>), dim3(nb), dim3(BLK), 0, g->stream, q, e->d_KE, a, xPhys, Emin, Emax, penal, dfdx, e->d_resp);
-        else
-            TP_LAUNCH((k_response<false, true>), dim3(nb), dim3(BLK), 0, g->stream, q, e->d_KE, a, xPhys, Emin, Emax, penal, dfdx, e->d_resp);
-        count_launch(g, bytes, flops);
-        TP_TRY(reduce_partials_n(g, e->d_resp, nb, ncase + 1, S_TMP));
-        double v[TP_MAX_CASES + 1];
-        TP_TRY(read_scal(g, S_TMP, ncase + 1, v));
-        double f = 0.0;
-        for (int l = 0; l < ncase; l++) {
-            if (f_case) f_case[l] = v[l];
-            f = fma(a.w[l], v[l], f);
-        }
-        if (fx) *fx = f;
-        if (gx) *gx = v[ncase] / (double)nel_glob - volfrac;
-    }
-    if (dgdx) TP_TRY(tp_vec_set(g, dgdx, 1.0 / (double)nel_glob, nel));
-    return TP_OK;
-}
-
-// ---- relaxed von Mises stress at the element centroids, its p-norm and the ingredients of the p-norm's sensitivity
-// s_e = u_e^T M u_e (M = B0^T C^T Vm C B0, elements.h), vm_e = Emax x_e^q sqrt(s_e), pnorm = (sum_e vm_e^P)^(1/P).
-// Both kernels take u_e RELATIVE TO THE ELEMENT'S CORNER 0 (d_a = u_a - u_0): M annihilates translations, so the value is
-// the same to rounding, an element in rigid translation gets s_e = 0 and M d_e = 0 EXACTLY instead of a rounding residue
-// under a square root, and the three columns of corner 0 drop out (441 fma instead of 576).  Indices into M are compile-time
-// constants: scalar operand loads, as for KE in k_objective.
-// Pass 1, one thread per own element like k_objective: vm_e (if asked), s_e (clamped at 0) for the later passes, and with
-// REDUCE the block partials of vm_e^P and of max vm_e, partials[value][block].
-template <bool REDUCE>
-__global__ __launch_bounds__(BLK) void k_stress_elem(Geom g, const double *__restrict__ M, const double *__restrict__ U,
-                                                     const double *__restrict__ x, double Emax, double q, double P,
-                                                     double *__restrict__ vm_out, double *__restrict__ s_out,
-                                                     double *__restrict__ partials) {
-    const long nel = g.own_elems();
-    const long t = blockIdx.x * (long)BLK + threadIdx.x;
-    double vm = 0.0;
-    if (t < nel) {
-        const int i = (int)(t % g.ex), j = (int)((t / g.ex) % g.ey), k = (int)(t / ((long)g.ex * g.ey));
-        double d[24];
-#pragma unroll
-        for (int a = 0; a < 8; a++) {
-            const long nd = (long)(i + LXc(a)) + (long)g.nx * ((j + LYc(a)) + (long)g.ny * (k + LZc(a)));
-#pragma unroll
-            for (int c = 0; c < 3; c++) d[3 * a + c] = U[3 * nd + c];
-        }
-#pragma unroll
-        for (int r = 3; r < 24; r++) d[r] -= d[r % 3];
-        double s = 0.0;
-#pragma unroll
-        for (int r = 3; r < 24; r++) {
-            double m = 0.0;
-#pragma unroll
-            for (int c = 3; c < 24; c++) m = fma(M[r * 24 + c], d[c], m);
-            s = fma(d[r], m, s);
-        }
-        s = s < 0.0 ? 0.0 : s;  // (M is positive semi-definite; a strain at rounding level may come out below zero; NaN stays)
-        if (s != 0.0) vm = Emax * pow(x[t], q) * sqrt(s);
-        if (vm_out) vm_out[t] = vm;
-        if (s_out) s_out[t] = s;
-    }
-    if (!REDUCE) return;
-    const double sp = block_sum(vm != 0.0 ? pow(vm, P) : 0.0);
-    const double mx = block_max(vm);  // (fmax drops a NaN; the sum carries it: a NaN state gives pnorm = NaN as it gives fx = NaN)
-    if (threadIdx.x == 0) {
-        partials[blockIdx.x] = sp;
-        partials[gridDim.x + blockIdx.x] = mx;
-    }
-}
-// out[0] = sum of the first nb partials, out[1] = max of the second nb, fixed order
-__global__ __launch_bounds__(BLK) void k_stress_reduce(const double *__restrict__ partials, int nb, double *__restrict__ out) {
-    double s = 0.0, m = 0.0;
-    for (int b = threadIdx.x; b < nb; b += BLK) {
-        s += partials[b];
-        m = fmax(m, partials[nb + b]);
-    }
-    s = block_sum(s);
-    m = block_max(m);
-    if (threadIdx.x == 0) {
-        out[0] = s;
-        out[1] = m;
-    }
-}
-// Between the passes, once pnorm is known: s_e -> c_e = pnorm^(1-P) (Emax x^q)^P s_e^((P-2)/2), the weight of L_e^T M u_e in
-// d pnorm / dU, formed as r_e^(P-2) (Emax x^q)^2 / pnorm with r_e = vm_e / pnorm <= 1 (no overflow, no division by s_e),
-// in place; and the explicit part dpdx_e = pnorm^(1-P) q Emax^P x^(qP-1) s_e^(P/2) in the power form q pnorm x^(qP-1)
-// (Emax sqrt(s_e) / pnorm)^P: x_e = 0 gives 0 (qP > 1) or a finite value (qP = 1), never NaN.  s_e = 0 or pnorm = 0: both 0.
-__global__ __launch_bounds__(BLK) void k_stress_coef(long nel, const double *__restrict__ x, double Emax, double q, double P,
-                                                     double pnorm, double *__restrict__ sc, double *__restrict__ dpdx) {
-    for (long t = blockIdx.x * (long)BLK + threadIdx.x; t < nel; t += (long)gridDim.x * BLK) {
-        const double s = sc[t], xe = x[t];
-        double c = 0.0, dp = 0.0;
-        if (pnorm != 0.0 && s != 0.0) {
-            const double a = Emax * pow(xe, q), rs = sqrt(s);
-            c = pow(a * rs / pnorm, P - 2.0) * a * (a / pnorm);
-            if (q != 0.0) dp = q * pnorm * pow(xe, q * P - 1.0) * pow(Emax * rs / pnorm, P);
-        }
-        sc[t] = c;
-        if (dpdx) dpdx[t] = dp;
-    }
-}
-// Pass 2, one thread per OWNED node: adj_rhs = sum over the node's <= 8 incident elements, in a fixed order, of
-// c_e (M d_e)[rows of the node's corner] -- a gather, no atomics, bit-reproducible.  Incident element n8 of the unrolled
-// loop lies at (i - dx, j - dy, k - dz) and has the node as its corner corner_of(dx, dy, dz) for every thread: the three rows
-// of M are compile-time.  Elements outside the mesh or the slab (layers 0 .. ezl - 1: own + the ghost layer above, whose
-// c_e came from the upper neighbour) are skipped, and so are those with c_e = 0.  The Dirichlet mask is not applied here.
-__global__ __launch_bounds__(BLK) void k_stress_adjoint_rhs(Geom g, const double *__restrict__ M, const double *__restrict__ U,
-                                                            const double *__restrict__ ce, double *__restrict__ out) {
-    const long t = blockIdx.x * (long)BLK + threadIdx.x;
-    if (t >= g.owned_nodes()) return;
-    const long n = g.plane() * g.own_lo + t;
-    const int i = (int)(n % g.nx), j = (int)((n / g.nx) % g.ny), k = (int)(n / g.plane());
-    double acc[3] = {0.0, 0.0, 0.0};
-#pragma unroll
-    for (int n8 = 0; n8 < 8; n8++) {
-        const int dx = n8 & 1, dy = (n8 >> 1) & 1, dz = n8 >> 2;
-        const int a = corner_of(dx, dy, dz);
-        const int ei = i - dx, ej = j - dy, ek = k - dz;
-        if (ei < 0 || ei >= g.ex || ej < 0 || ej >= g.ey || ek < 0 || ek >= g.ezl) continue;
-        const double c = ce[(long)ei + (long)g.ex * (ej + (long)g.ey * ek)];
-        if (c == 0.0) continue;
-        double d[24];
-#pragma unroll
-        for (int b = 0; b < 8; b++) {
-            const long nd = (long)(ei + LXc(b)) + (long)g.nx * ((ej + LYc(b)) + (long)g.ny * (ek + LZc(b)));
-#pragma unroll
-            for (int cc = 0; cc < 3; cc++) d[3 * b + cc] = U[3 * nd + cc];
-        }
-#pragma unroll
-        for (int r = 3; r < 24; r++) d[r] -= d[r % 3];
-#pragma unroll
-        for (int r = 0; r < 3; r++) {
-            double m = 0.0;
-#pragma unroll
-            for (int cc = 3; cc < 24; cc++) m = fma(M[(3 * a + r) * 24 + cc], d[cc], m);
-            acc[r] = fma(c, m, acc[r]);
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < 3; r++) out[3 * n + r] = acc[r];
-}
-
-extern "C" int tp_elasticity_get_stress_form(const tp_elasticity *e, double *m) {
-    if (!e || !m) return TP_ERR_ARG;
-    std::memcpy(m, e->VM, sizeof(e->VM));
-    return TP_OK;
-}
-extern "C" int tp_elasticity_stress(tp_elasticity *e, const double *U, const double *xPhys, double Emax, double q, double P,
-                                    double *vm, double *pnorm, double *vm_max, double *dpdx, double *adj_rhs) {
-    if (!e || !U || !xPhys) return TP_ERR_ARG;
-    if (!(P >= 2.0) || !(q >= 0.0) || !(q == 0.0 || q * P >= 1.0)) return TP_ERR_ARG;
-    tp_grid *g = e->grid;
-    Geom geo = e->mg.lv[0].g;
-    const long nel = geo.own_elems(), lay = (long)geo.ex * geo.ey;
-    const bool sums = pnorm || vm_max || dpdx || adj_rhs;
-    if (!sums && !vm) return TP_OK;
-    TP_TRY(halo_nodes(g, geo, const_cast<double *>(U), 3));
-    const int nb = (int)((nel + BLK - 1) / BLK);
-    const double bytes = 24.0 * geo.owned_nodes() + 8.0 * nel, flops = 2.0 * 462 * nel;
-    if (!sums) {  // the field alone: no reduction, nothing for the host to wait for
-        TP_LAUNCH(k_stress_elem<false>, dim3(nb), dim3(BLK), 0, g->stream, geo, e->d_VM, U, xPhys, Emax, q, P, vm, (double *)nullptr,
-                  (double *)nullptr);
-        count_launch(g, bytes + 8.0 * nel, flops);
-        return TP_OK;
-    }
-    double *sc = nullptr;
-    if (dpdx || adj_rhs) {
-        if (!e->d_sx) {
-            TP_HIP(hipMalloc((void **)&e->d_sx, sizeof(double) * (size_t)(nel + lay)));
-            TP_HIP(hipMemsetAsync(e->d_sx, 0, sizeof(double) * (size_t)(nel + lay), g->stream));
-        }
-        sc = e->d_sx;
-    }
-    TP_LAUNCH(k_stress_elem<true>, dim3(nb), dim3(BLK), 0, g->stream, geo, e->d_VM, U, xPhys, Emax, q, P, vm, sc, g->partials);
-    count_launch(g, bytes + 8.0 * nel * ((vm ? 1 : 0) + (sc ? 1 : 0)), flops);
-    TP_LAUNCH(k_stress_reduce, dim3(1), dim3(BLK), 0, g->stream, g->partials, nb, g->scal + S_TMP);
-    count_launch(g);
-    TP_TRY(finish_reduction_n(g, S_TMP, 1));  // the sum over the ranks; the maximum follows below
-    double v[2];
-    TP_TRY(read_scal(g, S_TMP, 2, v));
-    if (g->has_comm) {
-        // max over ranks through the sum hook: every rank's value in its own slot, 16 slots at a time (as tp_mma_design_change)
-        const double mine = v[1];
-        for (int o = 0; o < g->nranks; o += 16) {
-            const int cnt = g->nranks - o < 16 ? g->nranks - o : 16;
-            double slots[16] = {0};
-            if (g->rank >= o && g->rank < o + cnt) slots[g->rank - o] = mine;
-            TP_HIP(hipMemcpyAsync(g->comm.red, slots, sizeof(double) * cnt, hipMemcpyHostToDevice, g->stream));
-            TP_HIP(hipStreamSynchronize(g->stream));  // `slots` is a stack buffer
-            if (g->comm.allreduce_sum(g->comm.user, cnt)) return TP_ERR_COMM;
-            TP_HIP(hipMemcpyAsync(g->h_scal, g->comm.red, sizeof(double) * cnt, hipMemcpyDeviceToHost, g->stream));
-            TP_HIP(hipStreamSynchronize(g->stream));
-            for (int r = 0; r < cnt; r++) v[1] = fmax(v[1], g->h_scal[r]);
-        }
-    }
-    const double pn = v[0] != 0.0 ? pow(v[0], 1.0 / P) : 0.0;
-    if (pnorm) *pnorm = pn;
-    if (vm_max) *vm_max = v[1];
-    if (!sc) return TP_OK;
-    TP_LAUNCH(k_stress_coef, dim3(grid_for(nel)), dim3(BLK), 0, g->stream, nel, xPhys, Emax, q, P, pn, sc, dpdx);
-    count_launch(g, (24.0 + (dpdx ? 8.0 : 0.0)) * nel, 8.0 * nel);
-    if (!adj_rhs) return TP_OK;
-    // the ghost element layer above <- the upper neighbour's first own layer, the way tp_elasticity_assemble fills d_E
-    TP_TRY(exchange_segments(g, sc, nullptr, nullptr, sc + nel, lay, 1, lay));
-    const long nown = geo.owned_nodes();
-    TP_LAUNCH(k_stress_adjoint_rhs, dim3((int)((nown + BLK - 1) / BLK)), dim3(BLK), 0, g->stream, geo, e->d_VM, U, sc, adj_rhs);
-    count_launch(g, 48.0 * nown + 8.0 * nel, 2.0 * 8 * (63 + 3) * nown);
-    return TP_OK;
-}
-
-// ---- self-weight: design-dependent body force, its nodal load and its sensitivity term
-#include "bodyforce.h"
-
 extern "C" int tp_elasticity_set_tolerances(tp_elasticity *e, double rtol, double atol, double dtol, int max_it) {
     if (!e) return TP_ERR_ARG;   // KSPSetTolerances (LinearElasticity.cc:646); negative = keep (PETSC_DEFAULT)
     if (rtol >= 0) e->mg.opt.rtol = rtol;
@@ -1800,6 +1391,13 @@ extern "C" int tp_elasticity_last_op_form(const tp_elasticity *e, int *form4) {
     for (int i = 0; i < 4; i++) form4[i] = e->mg.last_form[i];
     return TP_OK;
 }
+
+// ===========================================================================
+// responses of the state: compliance of one or several load cases, von Mises stress p-norm, self-weight
+// ===========================================================================
+#include "response.h"
+#include "stress.h"
+#include "bodyforce.h"
 
 // ===========================================================================
 // density / sensitivity filter and Helmholtz PDE filter
