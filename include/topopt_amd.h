@@ -355,7 +355,9 @@ int tp_elasticity_last_stats(const tp_elasticity *e, double *alg_bytes, double *
 /* which kernel form the last operator application (apply, level_apply, smooth, ...) launched, for tests that force a form
  * through the environment and must not pass on another one: form4[0] 1 fine tile kernel, 2 level 1 applied from the fine
  * densities, 3 per-node matrix-free kernel, 4 stored stencil; [1] fine: generation 1..3, level 1: 1 if the Dirichlet
- * correction was fused, stencil: threads per row 9 / 3 / 1; [2] fine: tile 0 = 15 x 15 nodes, 1 = 16x16, 2 = 32x8,
+ * correction was fused, per-node kernel: 1 if it applied the scalar (Helmholtz) operator from its 27-point weight table,
+ * 0 for the gather over the elements (elasticity always; the PDE filter with TP_NO_PDE_STENCIL), stencil: threads per
+ * row 9 / 3 / 1; [2] fine: tile 0 = 15 x 15 nodes, 1 = 16x16, 2 = 32x8,
  * 3 = 32x16, stencil: 1 = node form; [3] fine and level 1: z-chunk length, stencil: 1 = mirrored reads */
 int tp_elasticity_last_op_form(const tp_elasticity *e, int *form4);
 
@@ -389,6 +391,20 @@ int tp_pdefilter_elem_to_node(tp_filter *f, const double *x_elem, double *rhs_no
 int tp_pdefilter_solve(tp_filter *f, const double *rhs_nodal, double *u_nodal);
 int tp_pdefilter_node_to_elem(tp_filter *f, const double *u_nodal, double *x_elem);
 int tp_pdefilter_apply(tp_filter *f, const double *u_nodal, double *y_nodal);
+/* The PDE filter's scalar multigrid hierarchy level by level, for tests: the counterparts of tp_elasticity_level_*,
+ * _smooth, _restrict, _prolong_add and _last_op_form (level 0 of level_apply is tp_pdefilter_apply; level_diag exports
+ * the reciprocal Jacobi diagonal).  Vectors: [dev, the level's local nodes].  A filter that is not of type 2, a level
+ * it does not have or a null vector: TP_ERR_ARG (-TP_ERR_ARG from level_count / level_nodes, NaN from the lambdas). */
+int tp_pdefilter_level_count(const tp_filter *f);
+long tp_pdefilter_level_nodes(const tp_filter *f, int level);
+double tp_pdefilter_level_lambda(const tp_filter *f, int level);
+double tp_pdefilter_level_lambda_min(const tp_filter *f, int level);
+int tp_pdefilter_level_apply(tp_filter *f, int level, const double *u, double *y);
+int tp_pdefilter_level_diag(tp_filter *f, int level, double *dinv);
+int tp_pdefilter_smooth(tp_filter *f, int level, const double *b, double *x, int k, int zero_guess);
+int tp_pdefilter_restrict(tp_filter *f, int level, const double *rf, double *rc);
+int tp_pdefilter_prolong_add(tp_filter *f, int level, const double *xc, double *xf);
+int tp_pdefilter_last_op_form(const tp_filter *f, int *form4);
 
 /* ---- local volume constraint (no reference counterpart; Wu, Aage, Westermann, Sigmund 2018) ---- */
 /* The mean density in a ball of radius R around every element, held below alpha through ONE p-norm constraint:

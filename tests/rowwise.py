@@ -17,6 +17,8 @@ row i (a majorant of it, computed with the float64 oracle -- its own rounding, 1
     dfdx         p x^(p-1) (Emax - Emin) max|KE| ||u_e||_1^2   per element
     cone filter  H'|x| / Hs + (H|x| / Hs) rho  with the majorant weights H' = H + (R + L) B (class Cone below: B the 0/1
                  pattern of H, L the largest element-centre coordinate, rho = (R + L) B1 / Hs); gradients: the same on |df|
+    Helmholtz filter   level l: |K_f|_l |u|, the scalar hierarchy assembled from abs(kf); element <-> node: T|x|, T^T|u|
+                 (the section "the Helmholtz (PDE) filter's scalar hierarchy" below)
 
 THE CONSTANTS c come from the length of the chain of rounded operations of the form, never from what the HIP kernels
 achieve; beside each: the count, and what the float64 oracle measures against the arbiter on the CPU
@@ -93,6 +95,201 @@ def c_filter(conn):
 
 def _pow2(v):
     return 1 << int(np.ceil(np.log2(v)))
+
+
+# =====================================================================================================================
+# the Helmholtz (PDE) filter's scalar hierarchy (tests/test_gpu_pde_rowwise.py): K_f of an anisotropic box, one 8 x 8 matrix per
+# level, no moduli and no Dirichlet rows.  Row scales: level l  |K_f|_l |u| -- the hierarchy assembled from abs(kf) applied to
+# abs(u): the transfer weights are non-negative, so the Galerkin product of |kf| majorises the terms of every coarse row and the
+# rounding of the coarse 8 x 8 matrices; transfers and the Chebyshev step as above; element <-> node  T|x| and T^T|u|; the
+# Jacobi diagonal relative to its own entry.
+# =====================================================================================================================
+def c_pde_level(l):
+    """K_f on level l.  Count: the gather form sums 8 elements x 8 corners (64 fma; the table form 7 additions per weight and 27
+    fma: 34), and per Galerkin step the sum over the children c and their corners a, b of W[c, a, I] KF[a, b] W[c, b, J]: of
+    its 512 terms at most 5^3 = 125 are non-zero (per axis the pairs (child, corner) that see a coarse node: 3 of 4; both
+    corners: 5 of 8 on the diagonal, 4 off it), the weights are powers of two: 64 + 125 l -> 64, 189, 314.  Oracle (assembled
+    CSR, Galerkin by sparse products) against arbiter, measured over the meshes, regimes and inputs of PDE_CASES and PDE_SLAB3:
+    4.88 / 4.81 / 3.38 on levels 0 / 1 / 2 (x 16 = 78, 77, 54): level 0 takes 128 from the measured value, the levels 1 and 2
+    take 256 and 512 from the count."""
+    return max(128, _pow2(64 + 125 * l))
+
+
+def c_pde_diag(l):
+    """the scalar Jacobi diagonal (exported as its reciprocal), RELATIVE to the row's own entry.  Count: the 8-element sum of
+    positive entries, the reciprocal and the test's own division back: 10, and 125 per Galerkin step: 10, 135, 260.  Oracle
+    against arbiter, measured: 1.84 / 4.49 / 7.59 on levels 0 / 1 / 2 (x 16 = 30, 72, 121) -> 32 from the measured value, 256
+    and 512 from the count.  (A coarse diagonal entry is the energy of a hat function, a sum of terms of both signs: where the
+    stiffness dominates, rmin / h = 100, its |kf| majorant is 3.0 times the entry on level 1 and 12.0 times on level 2 -- the
+    oracle's growing figures; a worst-case sum would need count x majorant, the bound keeps to the rule.)"""
+    return 32 if l == 0 else _pow2(10 + 125 * l)
+
+
+def c_pde_smooth(l):
+    """one Chebyshev step on level l with the level's STORED dinv: the product's count + 1/theta, b - Ax, x dinv, x 1/theta,
+    + x0 (5): 69, 194, 319 -> 128, 256, 512.  Oracle against arbiter, measured: 2.92 / 3.09 / 2.56 (x 16 <= 50)."""
+    return _pow2(69 + 125 * l)
+
+
+# the scalar transfers are the elasticity's with one component: C_RESTRICT, C_PROLONG.  Measured on PDE_CASES: 2.90 and 2.52
+# (x 16 = 46 and 40 -> 64 both).
+# element <-> node: 8 terms of 0.125 x (exact products), the first addition to 0 exact: 7 rounded additions -> 8, a bound that
+# holds for ANY float64 evaluation in that order.  (No oracle function: tests/test_rowwise_oracle.py holds a float64 numpy
+# restatement, summed in the kernels' order, to the same 8 -- it measures 3.04; the rule's 16 x measured = 64 would only be
+# looser than what the count already guarantees.)
+C_PDE_T = 8
+
+# elements, (hx, hy, hz) or None = cube of h = 1 / ey, levels, rmin / min(h)
+PDE_RATIOS = (0.08, 2.56, 100.0)     # mass term dominates / the project's default / stiffness dominates, rows cancel
+PDE_CASES = [
+    ((20, 12, 8), (0.05, 0.04, 0.03), 3, PDE_RATIOS),   # anisotropic; coarsest 5 x 3 x 2
+    ((8, 4, 4), None, 3, PDE_RATIOS),                   # coarsest 2 x 1 x 1: one element wide, every node in a boundary class
+    ((13, 7, 3), (0.1, 0.07, 0.2), 1, (2.56,)),         # odd sizes; 448 nodes
+    ((33, 4, 2), None, 1, (2.56,)),                     # 510 nodes: two workgroups, the second partly filled
+    ((36, 28, 20), (0.03, 0.04, 0.05), 3, (2.56,)),     # many workgroups on every level
+]
+PDE_SLABS = [(0, 2), (None, 3)]                         # (case, ranks); None: (8, 4, 12) cube below, three slabs
+PDE_SLAB3 = ((8, 4, 12), None, 3, (2.56,))
+_LX, _LY, _LZ = (0, 1, 1, 0, 0, 1, 1, 0), (0, 0, 1, 1, 0, 0, 1, 1), (0, 0, 0, 0, 1, 1, 1, 1)    # the reference's corner order
+
+
+def pde_box(case):
+    (ex, ey, ez), h = case[0], case[1]
+    return h if h is not None else (1.0 / ey,) * 3
+
+
+def pde_unit_nodes(dims):
+    """[(name, (a, b, a'))]: a corner, an edge, a face and an interior node a of the level (on a level one element wide: what
+    there is of them), its diagonal neighbour b (towards the inside) and its mirror image a' through the centre of the box"""
+    nx, ny, nz = dims
+    idx = lambda p: p[0] + nx * (p[1] + ny * p[2])
+    out = []
+    for name, a in (("corner", (0, 0, 0)), ("edge", (nx // 2, 0, 0)), ("face", (nx // 2, ny // 2, 0)), ("interior", (nx // 2, ny // 2, nz // 2))):
+        b = tuple(v + 1 if v + 1 < n else v - 1 for v, n in zip(a, dims))
+        am = tuple(n - 1 - v for v, n in zip(a, dims))
+        out.append((name, (idx(a), idx(b), idx(am))))
+    return out
+
+
+def pde_inputs(dims, seed):
+    """the inputs of one level: {name: vector}: seeded normal field (and a second one: right-hand side / coarse vector), the
+    constant 1, the linear field i + 2 j + 3 k, unit vectors (pde_unit_nodes)"""
+    nx, ny, nz = dims
+    n = nx * ny * nz
+    rng = np.random.default_rng(seed)
+    k, j, i = np.meshgrid(np.arange(nz), np.arange(ny), np.arange(nx), indexing="ij")
+    out = {"normal": rng.standard_normal(n), "b": rng.standard_normal(n), "one": np.ones(n), "linear": (i + 2.0 * j + 3.0 * k).reshape(-1)}
+    for name, nodes in pde_unit_nodes(dims):
+        for t, q in zip(("a", "b", "m"), nodes):
+            e = np.zeros(n)
+            e[q] = 1.0
+            out["unit_%s_%s" % (name, t)] = e
+    return out
+
+
+PDE_FIELDS = ("normal", "one", "linear")
+
+
+def pde_seed(m, r, l):
+    return 7000 + 100 * m + 10 * r + l
+
+
+def pde_t_inputs(m, nel, nn):
+    """the inputs of the element <-> node transfers of case m: {name: (element field, nodal field)}"""
+    rng = np.random.default_rng(pde_seed(m, 9, 9))
+    return {"seeded": (rng.random(nel), rng.random(nn)), "one": (np.ones(nel), np.ones(nn))}
+
+
+def pde_T(x, ex, ey, ez, dtype=np.float64):
+    """T x: node <- the eighth of every adjacent element, summed in the kernel's order (corner a = 0 .. 7 of the node)"""
+    p = np.zeros((ez + 2, ey + 2, ex + 2), dtype=dtype)
+    p[1:-1, 1:-1, 1:-1] = np.asarray(x, dtype=dtype).reshape(ez, ey, ex)
+    s = np.zeros((ez + 1, ey + 1, ex + 1), dtype=dtype)
+    for a in range(8):       # element (i - LX[a], j - LY[a], k - LZ[a]) -> padded index + 1
+        s += dtype(0.125) * p[1 - _LZ[a]:ez + 2 - _LZ[a], 1 - _LY[a]:ey + 2 - _LY[a], 1 - _LX[a]:ex + 2 - _LX[a]]
+    return s.reshape(-1)
+
+
+def pde_Tt(u, ex, ey, ez, dtype=np.float64):
+    """T^T u: element <- the eighth of each of its 8 nodes, in corner order"""
+    v = np.asarray(u, dtype=dtype).reshape(ez + 1, ey + 1, ex + 1)
+    s = np.zeros((ez, ey, ex), dtype=dtype)
+    for a in range(8):
+        s += dtype(0.125) * v[_LZ[a]:ez + _LZ[a], _LY[a]:ey + _LY[a], _LX[a]:ex + _LX[a]]
+    return s.reshape(-1)
+
+
+def pde_table(KF):
+    """numpy restatement of the 27 x 27 class table of the scalar operator from its 8 x 8 element matrix: W[class, offset],
+    class = (cz 3 + cy) 3 + cx with c = 0 no lower element / 1 both / 2 no upper element along the axis, offset =
+    (dz + 1) 9 + (dy + 1) 3 + (dx + 1); W = sum over the existing elements around the node (the node their corner a) of KF[a, b]
+    at the offset of corner b"""
+    KF = np.asarray(KF).reshape(8, 8)
+    W = np.zeros((27, 27), dtype=KF.dtype)
+    for cz in range(3):
+        for cy in range(3):
+            for cx in range(3):
+                w = W[(cz * 3 + cy) * 3 + cx]
+                for a in range(8):
+                    if any((c == 0) if l else (c == 2) for l, c in ((_LX[a], cx), (_LY[a], cy), (_LZ[a], cz))):
+                        continue
+                    for b in range(8):
+                        w[(_LZ[b] - _LZ[a] + 1) * 9 + (_LY[b] - _LY[a] + 1) * 3 + (_LX[b] - _LX[a] + 1)] += KF[a, b]
+    return W
+
+
+def pde_table_apply(W, dims, u):
+    """y = A u from the class table: what the table kernel computes, in numpy"""
+    nx, ny, nz = dims
+    cls = lambda n: np.where(np.arange(n) == 0, 0, np.where(np.arange(n) == n - 1, 2, 1))
+    cz, cy, cx = np.meshgrid(cls(nz), cls(ny), cls(nx), indexing="ij")
+    c = (cz * 3 + cy) * 3 + cx
+    p = np.zeros((nz + 2, ny + 2, nx + 2), dtype=W.dtype)
+    p[1:-1, 1:-1, 1:-1] = np.asarray(u, dtype=W.dtype).reshape(nz, ny, nx)
+    y = np.zeros((nz, ny, nx), dtype=W.dtype)
+    for dz in (-1, 0, 1):
+        for dy in (-1, 0, 1):
+            for dx in (-1, 0, 1):
+                y += W[c, (dz + 1) * 9 + (dy + 1) * 3 + (dx + 1)] * p[1 + dz:nz + 1 + dz, 1 + dy:ny + 1 + dy, 1 + dx:nx + 1 + dx]
+    return y.reshape(-1)
+
+
+def pde_galerkin(KF):
+    """the next coarser level's 8 x 8 matrix: sum over the 8 children c of W_c^T KF W_c, W_c[a, I] the trilinear weight of coarse
+    corner I at corner a of child c (constant coefficients: one matrix per level)"""
+    KF = np.asarray(KF).reshape(8, 8)
+    out = np.zeros((8, 8), dtype=KF.dtype)
+    for c in range(8):
+        Wc = np.zeros((8, 8), dtype=KF.dtype)
+        for a in range(8):
+            pos = (_LX[c] + _LX[a], _LY[c] + _LY[a], _LZ[c] + _LZ[a])          # fine coordinates 0 .. 2 inside the coarse element
+            for I in range(8):
+                w = 1.0
+                for q, L in zip(pos, (_LX[I], _LY[I], _LZ[I])):
+                    w *= (q / 2.0) if L else (1.0 - q / 2.0)
+                Wc[a, I] = w
+        out += Wc.T @ KF @ Wc
+    return out
+
+
+class PdeRef:
+    """The references of one filter: the float64 oracle hierarchy of kf (row scales of the transfers, the oracle's own figures),
+    the same of abs(kf) (row scales of the products) and the 80-bit arbiter's of kf."""
+
+    def __init__(self, orc, arb, dims, nlv, kf):
+        nx, ny, nz = dims
+        self.dims, self.nlv = dims, nlv
+        kf = np.asarray(kf, dtype=np.float64)
+        self.mg, self.mga, self.amg = orc.MG(nx, ny, nz, 1, nlv), orc.MG(nx, ny, nz, 1, nlv), arb.MG(nx, ny, nz, 1, nlv)
+        self.mg.assemble(kf)
+        self.mga.assemble(np.abs(kf))
+        self.amg.assemble(np.ascontiguousarray(kf, dtype=np.longdouble))
+
+    def scale(self, l, u):
+        return self.mga.apply(l, np.abs(np.asarray(u, dtype=np.float64)))
+
+    def theta(self, l, lam, lam_min):
+        return 0.5 * (1.1 * lam + (lam_min if (l == self.nlv - 1 and l > 0) else 0.1 * lam))
 
 
 # =====================================================================================================================

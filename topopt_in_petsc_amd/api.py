@@ -753,6 +753,72 @@ class Filter:
         """y = K_f u, the nodal Helmholtz operator of the PDE filter applied matrix-free (PDEFilter.cc:251-264 assembles it)"""
         _chk(self.L.tp_pdefilter_apply(self.handle, _ptr(u), _ptr(y)), "tp_pdefilter_apply")
 
+    def elem_to_node(self, x):
+        """PDE filter: T x, element -> node (the eighth of every adjacent element; PDEFilter.cc:198-202 without the volume)"""
+        y = self.grid.node_vec(1)
+        _chk(self.L.tp_pdefilter_elem_to_node(self.handle, _ptr(x), _ptr(y)), "tp_pdefilter_elem_to_node")
+        return y
+
+    def node_to_elem(self, u):
+        """PDE filter: T^T u, node -> element (PDEFilter.cc:210); refreshes the ghost planes of u"""
+        x = self.grid.elem_vec()
+        _chk(self.L.tp_pdefilter_node_to_elem(self.handle, _ptr(u), _ptr(x)), "tp_pdefilter_node_to_elem")
+        return x
+
+    # ---- the PDE filter's scalar hierarchy level by level (tests): as LinearElasticity.level_* / smooth / restrict / ...
+    def level_count(self):
+        n = self.L.tp_pdefilter_level_count(self.handle)
+        _chk(-n if n < 0 else 0, "tp_pdefilter_level_count")
+        return n
+
+    def level_nodes(self, l):
+        n = self.L.tp_pdefilter_level_nodes(self.handle, l)
+        _chk(-n if n < 0 else 0, "tp_pdefilter_level_nodes")
+        return n
+
+    def level_lambda(self, l):
+        v = self.L.tp_pdefilter_level_lambda(self.handle, l)
+        _chk(1 if v != v else 0, "tp_pdefilter_level_lambda")
+        return v
+
+    def level_lambda_min(self, l):
+        v = self.L.tp_pdefilter_level_lambda_min(self.handle, l)
+        _chk(1 if v != v else 0, "tp_pdefilter_level_lambda_min")
+        return v
+
+    def level_vec(self, l):
+        return torch.zeros(self.level_nodes(l), dtype=torch.float64, device=self.grid.device)
+
+    def level_apply(self, l, u):
+        y = torch.zeros_like(u)
+        _chk(self.L.tp_pdefilter_level_apply(self.handle, l, _ptr(u), _ptr(y)), "tp_pdefilter_level_apply")
+        return y
+
+    def level_dinv(self, l):
+        d = self.level_vec(l)
+        _chk(self.L.tp_pdefilter_level_diag(self.handle, l, _ptr(d)), "tp_pdefilter_level_diag")
+        return d
+
+    def smooth(self, l, b, x, k, zero_guess=False):
+        _chk(self.L.tp_pdefilter_smooth(self.handle, l, _ptr(b), _ptr(x), k, int(zero_guess)), "tp_pdefilter_smooth")
+        return x
+
+    def restrict(self, l, rf):
+        rc = self.level_vec(l + 1)
+        _chk(self.L.tp_pdefilter_restrict(self.handle, l, _ptr(rf), _ptr(rc)), "tp_pdefilter_restrict")
+        return rc
+
+    def prolong_add(self, l, xc, xf):
+        _chk(self.L.tp_pdefilter_prolong_add(self.handle, l, _ptr(xc), _ptr(xf)), "tp_pdefilter_prolong_add")
+        return xf
+
+    def last_op_form(self):
+        """(kind, a, b, c) of the scalar hierarchy's last operator launch: (3, 1, 0, 0) the 27-point weight table, (3, 0, 0, 0)
+        the gather over the elements (TP_NO_PDE_STENCIL)"""
+        f = (C.c_int * 4)()
+        _chk(self.L.tp_pdefilter_last_op_form(self.handle, f), "tp_pdefilter_last_op_form")
+        return tuple(f)
+
     def GetMND(self, x):
         v = C.c_double()
         _chk(self.L.tp_filter_mnd(self.handle, _ptr(x), C.byref(v)), "tp_filter_mnd")

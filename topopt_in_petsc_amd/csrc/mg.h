@@ -99,7 +99,8 @@ struct MGSolver {
     bool ready = false;
     int last_nblocks = 0;  // workgroups (= reduction partials) of the last op<EPI_APPLY_DOT>
     // what the last op<>() launched, for the tests (tp_elasticity_last_op_form): [0] 1 fine tile kernel, 2 level 1 from the fine
-    // densities, 3 per-node matrix-free, 4 stored stencil; [1] fine: generation, level 1: correction fused, stencil: row split;
+    // densities, 3 per-node matrix-free, 4 stored stencil; [1] fine: generation, level 1: correction fused, per-node: 1 = the scalar
+    // operator's 27-point table (ScalarStencilOp), 0 = the gather over the elements, stencil: row split;
     // [2] fine: tile 0 15 x 15 nodes, 1 16x16, 2 32x8, 3 32x16, stencil: node form; [3] fine, level 1: z-chunk, stencil: mirrored reads
     int last_form[4] = {0, 0, 0, 0};
     static constexpr int NLANCZOS_COARSE = 40;

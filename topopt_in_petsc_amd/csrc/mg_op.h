@@ -262,7 +262,7 @@ int MGSolver<DOF>::op_matfree_node(OpLaunch &c, const NodeArgs &a) {
         c.bytes = 16.0 * DOF * c.nown + (L.E ? 8.0 * L.g.own_elems() : 0.0);
         c.flops = 2.0 * (8 * DOF) * (8 * DOF) * (double)L.g.own_elems();
     }
-    last_form[0] = 3, last_form[1] = last_form[2] = last_form[3] = 0;
+    last_form[0] = 3, last_form[1] = as_stencil ? 1 : 0, last_form[2] = last_form[3] = 0;
     return TP_OK;
 }
 

@@ -141,6 +141,16 @@ SYMBOLS = {
     "tp_pdefilter_solve": (_i, [_vp, _vp, _vp]),
     "tp_pdefilter_node_to_elem": (_i, [_vp, _vp, _vp]),
     "tp_pdefilter_apply": (_i, [_vp, _vp, _vp]),
+    "tp_pdefilter_level_count": (_i, [_vp]),
+    "tp_pdefilter_level_nodes": (_l, [_vp, _i]),
+    "tp_pdefilter_level_lambda": (_d, [_vp, _i]),
+    "tp_pdefilter_level_lambda_min": (_d, [_vp, _i]),
+    "tp_pdefilter_level_apply": (_i, [_vp, _i, _vp, _vp]),
+    "tp_pdefilter_level_diag": (_i, [_vp, _i, _vp]),
+    "tp_pdefilter_smooth": (_i, [_vp, _i, _vp, _vp, _i, _i]),
+    "tp_pdefilter_restrict": (_i, [_vp, _i, _vp, _vp]),
+    "tp_pdefilter_prolong_add": (_i, [_vp, _i, _vp, _vp]),
+    "tp_pdefilter_last_op_form": (_i, [_vp, C.POINTER(_i)]),
     "tp_mma_create": (_i, [C.POINTER(_vp), _vp, _l, _l, _i, _vp]),
     "tp_mma_destroy": (_i, [_vp]),
     "tp_mma_set_outer_movelimit": (_i, [_vp, _d, _d, _d, _vp, _vp, _vp]),
