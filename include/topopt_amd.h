@@ -239,6 +239,10 @@ int tp_elasticity_apply(tp_elasticity *e, const double *u, double *y);
  * tp_elasticity_get_ke_krylov): KE's action to rounding on fields whose translation dominates their strain.
  * tp_elasticity_apply itself applies the packed form (tp_elasticity_get_ke_effective: within 5e-16 max|KE| of KE entrywise). */
 int tp_elasticity_apply_krylov(tp_elasticity *e, const double *u, double *y);
+/* The same call, which also returns the value of the product's fused dot product: *dot (host) = u . y summed over the owned
+ * dofs of all ranks -- CG's p . A p, accumulated per thread inside the kernel and finished by its reduction tail.  y is
+ * tp_elasticity_apply_krylov's bit for bit.  For tests of who owns a seam node in that sum. */
+int tp_elasticity_apply_krylov_dot(tp_elasticity *e, const double *u, double *y, double *dot);
 /* KSPSolve(ksp, RHS, U) with a warm start from U (:204, :647).  U, RHS [dev,
  * local nodes*3].  its / rnorm as KSPGetIterationNumber / KSPGetResidualNorm
  * (:212-213).  hist (host, may be NULL) receives ||b - A x_k|| for k = 0..its,
@@ -348,6 +352,15 @@ int tp_elasticity_level_gmres(tp_elasticity *e, int level, int pc, int m, int it
                               int zero_guess, int *its_done);
 /* k Chebyshev-Jacobi steps on a level (the fused operator+update kernel): x <- smooth(b, x) */
 int tp_elasticity_smooth(tp_elasticity *e, int level, const double *b, double *x, int k, int zero_guess);
+/* The same sweep with the LAST step's fused dot product: *dot (host) = b . x_out, the r . z that the V-cycle's last
+ * post-smoothing step hands to CG; x is tp_elasticity_smooth's bit for bit.  TP_ERR_STATE where the level's kernel carries no
+ * fused dot (anything but the fine tile kernels of generation 2 and 3), TP_ERR_ARG where no operator step would run
+ * (k < 1; the zero guess with k < 2: its first step is a scaling). */
+int tp_elasticity_smooth_dot(tp_elasticity *e, int level, const double *b, double *x, int k, int zero_guess, double *dot);
+/* r = b - A_level x through the residual epilogue of the level's operator kernel, as the V-cycle forms it before every
+ * restriction (the ghost planes of x are refreshed first; r is valid on the owned planes).  On level 0 the operator is the
+ * preconditioner's packed form (tp_elasticity_get_ke_effective), not the Krylov product. */
+int tp_elasticity_level_residual(tp_elasticity *e, int level, const double *b, const double *x, double *r);
 int tp_elasticity_restrict(tp_elasticity *e, int level, const double *rf, double *rc);
 int tp_elasticity_prolong_add(tp_elasticity *e, int level, const double *xc, double *xf);
 /* bytes moved / flops of the last call, by the algorithmic model of DESIGN.md */

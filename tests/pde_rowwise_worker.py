@@ -1,6 +1,6 @@
 """Worker of tests/test_gpu_pde_rowwise.py: the Helmholtz (PDE) filter's scalar hierarchy kernel by kernel.  The library latches
 its switches once per process, so there is one process per form; it runs every mesh, regime and input of rw.PDE_CASES through
-Filter.level_apply / level_dinv / smooth / restrict / prolong_add / elem_to_node / node_to_elem, ASSERTS after every operator
+Filter.level_apply / level_dinv / smooth (one step; on the first rw.PDE_STEP_CASES cases also steps 2 and 3 of a sweep) / restrict / prolong_add / elem_to_node / node_to_elem, ASSERTS after every operator
 call that the forced form is the one that launched (Filter.last_op_form) and dumps the outputs to one .npz (the inputs are
 rw.pde_inputs on both sides); the parent compares them with the 80-bit arbiter.
 
@@ -86,6 +86,12 @@ def single(expect, res):
                 res["%s_cheb0_%d" % (tag, l)] = host(f.smooth(l, dev(b), torch.zeros_like(dev(b)), 1, True))
                 res["%s_cheb1_%d" % (tag, l)] = host(f.smooth(l, dev(b), dev(u), 1, False))
                 check(f.last_op_form(), expect, "%s level %d Chebyshev step" % (tag, l))
+                if m < rw.PDE_STEP_CASES:       # steps 2, 3 of the sweeps from the zero guess and from u: the device's own iterates
+                    for zero in (1, 0):
+                        for j in range(1, max(rw.STEP_KS) + 1):
+                            x0 = torch.zeros_like(dev(b)) if zero else dev(u)
+                            res["%s_l%d_z%d_x%d" % (tag, l, zero, j)] = host(f.smooth(l, dev(b), x0, j, bool(zero)))
+                    check(f.last_op_form(), expect, "%s level %d Chebyshev step %d" % (tag, l, max(rw.STEP_KS)))
                 if l + 1 < nlv:
                     xc = rw.pde_inputs(rw.level_dims(nx, ny, nz, l + 1), rw.pde_seed(m, r, l + 1))
                     for name in rw.PDE_FIELDS:

@@ -69,6 +69,50 @@ def c_smooth(l):
     return _pow2(66) if l == 0 else _pow2(94 + 56 * l)
 
 
+def c_smooth_k(l):
+    """step k >= 2 of a sweep, x_k = x_{k-1} + c1 (x_{k-1} - x_{k-2}) + c2 dinv (b - A x_{k-1}), the reference step formed in 80-bit
+    arithmetic from the DEVICE's own x_{k-1}, x_{k-2}, dinv and window.  Count: c_smooth(l)'s + the subtraction, its product
+    with c1, the sum with the residual term, and one unit for the levels that keep the direction d = x_{k-1} - x_{k-2} as a
+    stored vector (it differs from the difference of the stored iterates by <= eps |x_{k-1}|, which the scale's first term
+    carries): + 4 -> 70 -> 128 on level 0, 98 + 56 l -> 154, 210, 266 -> 256 / 256 / 512 on levels 1 / 2 / 3.  Oracle against
+    arbiter (step k from the oracle's own x_{k-1}, x_{k-2}; k = 2, 3, 4 and 20 on the coarsest level), measured on the meshes of
+    tests/test_rowwise_oracle.py: 1.97 / 1.23 / 0.74 on levels 0 / 1 / 2 (x 16 = 32, 20, 12)."""
+    return _pow2(70) if l == 0 else _pow2(98 + 56 * l)
+
+
+def c_resid(l):
+    """the V-cycle's residual r = b - A_l x (EPI_RESID).  Count: the product's chain (C_FINE's 50, c_level(l)'s 89 + 56 l) + the
+    subtraction: 51 -> 64 = C_FINE on level 0, 90 + 56 l -> 256 / 256 / 512 = c_level(l) above.  Oracle against arbiter,
+    measured: 1.07 / 4.16 / 3.82 on levels 0 / 1 / 2 (x 16 = 18, 67, 62)."""
+    return _pow2(51) if l == 0 else _pow2(90 + 56 * l)
+
+
+def dot_chain(kz, nwg):
+    """longest chain of additions a term of a fused dot product passes through (EPI_APPLY_DOT's u . A u, EPI_CHEB_DOT's b . x_out):
+    the thread's fma chain over the kz planes of its z-chunk x 3 components (per-node kernel: kz = 1), the workgroup's sum
+    (wave_sum's 6 shuffle stages, then the 4 waves' sums added in turn), and the reduction tail over the nwg partials (a thread
+    of the last workgroup adds every 256th partial: ceil(nwg / 256); then the workgroup's sum again): 3 kz + 20 + ceil(nwg / 256)"""
+    return 3 * kz + 20 + (nwg + 255) // 256
+
+
+def c_dot(kz, nwg):
+    """|got - sum| <= c eps sum |terms|, the sum formed in 80-bit arithmetic from the device's OWN vectors (the products inside the
+    fma are exact): c = the chain's length rounded up to a power of two.  Such a bound holds for any float64 summation of that
+    depth: no oracle figure, like C_PDE_T."""
+    return _pow2(dot_chain(kz, nwg))
+
+
+def dot_workgroups(form, dims):
+    """workgroups (= partials) of a fused-dot launch over the whole level: form as last_op_form returns it, dims the node counts"""
+    nx, ny, nz = dims
+    kind, _, shape, kz = (int(v) for v in form)
+    if kind == 3:                           # a thread per node
+        return (nx * ny * nz + 255) // 256
+    assert kind == 1 and kz >= 1, form
+    tiles = ((nx + 30) // 31) * ((ny + 6) // 7) if shape == 2 else ((nx + 14) // 15) * ((ny + 14) // 15)
+    return tiles * ((nz + kz - 1) // kz)
+
+
 # dfdx per element: u_e^T KE u_e as 24 dot products of 24 terms and a 24-term sum (48), pow(x, p - 1) (<= 2), three scale
 # factors (3): 53.  Measured: 6.91 (x 16 = 111 -> 128).
 C_DFDX = 128
@@ -81,6 +125,12 @@ FILTER_MESH = (26, 22, 20)      # cone filter: ElemConn 10 needs 20 elements eve
 FILTER_RFACS = (1.5, 2.56, 5.12, 10.24)   # ElemConn 1, 2 (tiled), 5 (wide), 10 (streamed ring)
 FINE_MESHES = [(14, 6, 2), (15, 7, 3), (16, 8, 44), (30, 14, 7), (31, 15, 12), (32, 6, 9), (61, 8, 16), (62, 15, 44), (31, 17, 5), (33, 4, 2)]
 COARSE_MESHES = [((36, 28, 20), 3), ((40, 24, 16), 4)]
+# later Chebyshev steps, the residual epilogue and the fused dot products (the arbiter's products of the device's own iterates
+# cannot be shared between forms): smaller than one tile / the seams of both tile shapes / 45 planes, more than one z-chunk
+STEP_MESHES = [(14, 6, 2), (31, 15, 12), (16, 8, 44)]
+STEP_KS = (2, 3)                # step k of a sweep from a zero and from a non-zero guess; the coarsest level also STEP_K_COARSEST
+CG_FUSION_KINDS = ("blocks", "checker", "zlayer")       # tests/test_gpu_cg_fusions.py, on COARSE_MESHES
+STEP_K_COARSEST = 20            # (from the zero guess the default there is the one-launch run, coarse_run.h)
 
 
 def c_filter(conn):
@@ -131,6 +181,12 @@ def c_pde_smooth(l):
     return _pow2(69 + 125 * l)
 
 
+def c_pde_smooth_k(l):
+    """step k >= 2 of a sweep on level l (c_smooth_k's form and reference): c_pde_smooth's count + 4: 73, 198, 323 -> 128, 256,
+    512.  Oracle against arbiter, measured on PDE_CASES (k = 2, 3): 3.63 / 2.49 / 1.53 (x 16 <= 59)."""
+    return _pow2(73 + 125 * l)
+
+
 # the scalar transfers are the elasticity's with one component: C_RESTRICT, C_PROLONG.  Measured on PDE_CASES: 2.90 and 2.52
 # (x 16 = 46 and 40 -> 64 both).
 # element <-> node: 8 terms of 0.125 x (exact products), the first addition to 0 exact: 7 rounded additions -> 8, a bound that
@@ -148,6 +204,7 @@ PDE_CASES = [
     ((33, 4, 2), None, 1, (2.56,)),                     # 510 nodes: two workgroups, the second partly filled
     ((36, 28, 20), (0.03, 0.04, 0.05), 3, (2.56,)),     # many workgroups on every level
 ]
+PDE_STEP_CASES = 2                                      # later Chebyshev steps (STEP_KS): the first two cases, all their regimes
 PDE_SLABS = [(0, 2), (None, 3)]                         # (case, ranks); None: (8, 4, 12) cube below, three slabs
 PDE_SLAB3 = ((8, 4, 12), None, 3, (2.56,))
 _LX, _LY, _LZ = (0, 1, 1, 0, 0, 1, 1, 0), (0, 0, 1, 1, 0, 0, 1, 1), (0, 0, 0, 0, 1, 1, 1, 1)    # the reference's corner order
@@ -382,6 +439,28 @@ def scale_prolong_add(mg, l, xc, xf):
 def scale_smooth(s_x0, dinv, inv_theta, b, x0):
     """|x0| + c dinv (|b| + S_l(|x0|)); s_x0 = S_l(|x0|) (zeros for a zero guess)"""
     return np.abs(x0) + inv_theta * np.abs(dinv) * (np.abs(b) + s_x0)
+
+
+def cheb_coeffs(theta, delta, k):
+    """(c1, c2) of step k >= 2 of a sweep, by MGSolver::smooth's recurrence in float64 (the host code's own arithmetic)"""
+    sigma = theta / delta
+    rho = 1.0 / sigma
+    for _ in range(1, k):
+        rn = 1.0 / (2.0 * sigma - rho)
+        c1, c2 = rn * rho, 2.0 * rn / delta
+        rho = rn
+    return c1, c2
+
+
+def step_k_ref(x1, x2, c1, c2, dinv, b, Ax1_ld):
+    """x_k in 80-bit arithmetic from x_{k-1}, x_{k-2} and the arbiter's A x_{k-1}"""
+    L = lambda a: np.asarray(a, dtype=np.longdouble)
+    return L(x1) + np.longdouble(c1) * (L(x1) - L(x2)) + np.longdouble(c2) * L(dinv) * (L(b) - Ax1_ld)
+
+
+def scale_smooth_k(s_x1, dinv, c1, c2, b, x1, x2):
+    """|x_{k-1}| + c1 (|x_{k-1}| + |x_{k-2}|) + c2 dinv (|b| + S_l(|x_{k-1}|)); s_x1 = S_l(|x_{k-1}|)"""
+    return np.abs(x1) + abs(c1) * (np.abs(x1) + np.abs(x2)) + abs(c2) * np.abs(dinv) * (np.abs(b) + s_x1)
 
 
 def elem_u1(nx, ny, nz, U):

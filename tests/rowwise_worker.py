@@ -5,6 +5,8 @@ condition and 0/1 design of its job through the kernels, asserts that the FORCED
 usage: rowwise_worker.py filter <conn:kernel,...> <out.npz>      kernel as Filter.last_kernel returns it
        rowwise_worker.py fine <expect> <out.npz>
        rowwise_worker.py coarse <expect of the levels >= 2> <out.npz> <expect of level 1> <0|1: dfdx on a solved state too>
+       rowwise_worker.py fine_steps <expect> <out.npz>          later Chebyshev steps, residual epilogue, fused dot products
+       rowwise_worker.py coarse_steps <expect of the levels >= 2> <out.npz> <expect of level 1>       the same on every level
 expect: "kind,a,b,c" as last_op_form returns them, '*' = any, '<=n' = at most n"""
 import os
 import sys
@@ -131,6 +133,117 @@ def coarse(expect, res, lvl1, dfdx):
         grid.close()
 
 
+def sweeps(le, l, b, u, ks, res, t):
+    """the device's own iterates x_{k-2}, x_{k-1}, x_k of the sweeps from the zero guess and from u: res[t_z<zero>_x<j>]"""
+    for zero in (1, 0):
+        for j in sorted({j for k in ks for j in (k - 2, k - 1, k) if j > 0}):
+            x0 = torch.zeros_like(dev(b)) if zero else dev(u)
+            res["%s_z%d_x%d" % (t, zero, j)] = host(le.smooth(l, dev(b), x0, j, bool(zero)))
+
+
+def fine_steps(expect, res):
+    from oracle import oracle as orc
+    gen = None
+    for m, (ex, ey, ez) in enumerate(rw.STEP_MESHES):
+        nx, ny, nz, h = ex + 1, ey + 1, ez + 1, 1.0 / ey
+        for scattered in (0, 1):
+            rng = np.random.default_rng(300 + 10 * m + scattered)
+            grid = tp.Grid(nx, ny, nz, h)
+            le = tp.LinearElasticity(grid, tp.SolverOptions(nlvls=1))
+            bc(le, nx, ny, nz, scattered, rng)
+            n = 3 * nx * ny * nz
+            u, b = rng.standard_normal(n), rng.standard_normal(n)
+            tag = "m%d_s%d" % (m, scattered)
+            N = host(le.N)
+            res[tag + "_N"], res[tag + "_u"], res[tag + "_b"] = N, u, b
+            res[tag + "_kf"], res[tag + "_KE"] = le.KE_effective(), le.KE
+            # the chunk lengths of every launch under test (they may differ), from a first assembly
+            le.AssembleStiffnessMatrix(dev(rw.design("one_void", ex, ey, ez)), 1e-9, 1.0, 3.0)
+            kzs = []
+            for call in (lambda: le.smooth(0, dev(b), dev(u), 2, False), lambda: le.level_residual(0, dev(b), dev(u)),
+                         lambda: le.MatMultKrylovDot(dev(u))):
+                call()
+                kzs.append(le.last_op_form()[3] or 8)
+            for kind in rw.GENERATORS:
+                x = rw.design(kind, ex, ey, ez, tuple(kzs))
+                le.AssembleStiffnessMatrix(dev(x), 1e-9, 1.0, 3.0)
+                t = "%s_%s" % (tag, kind)
+                res[t + "_x"] = x
+                sweeps(le, 0, b, u, rw.STEP_KS, res, t)
+                check(le.last_op_form(), expect, "%s Chebyshev step %d" % (t, max(rw.STEP_KS)))
+                res[t + "_formk"] = np.asarray(le.last_op_form())
+                res[t + "_dinv"] = host(le.level_dinv(0))
+                res[t + "_lam"] = np.asarray([le.level_lambda(0), le.level_lambda_min(0)])
+                res[t + "_resid"] = host(le.level_residual(0, dev(b), dev(u)))
+                check(le.last_op_form(), expect, "%s residual" % t)
+                res[t + "_formr"] = np.asarray(le.last_op_form())
+                # ---- the fused dot products: the seeded fields, and the same set to zero wherever the row's scale exceeds 1e-6 of
+                # the largest -- a sum of void terms only
+                s = rw.scale_fine(orc, nx, ny, nz, le.KE, orc.simp(x), u, N)
+                void = s <= 1e-6 * s.max()
+                for name, uu, bb in (("n", u, b), ("v", u * void, b * void)):
+                    res["%s_dot_%s_u" % (t, name)], res["%s_dot_%s_b" % (t, name)] = uu, bb
+                    y, d = le.MatMultKrylovDot(dev(uu))
+                    form = le.last_op_form()
+                    check(form, expect, "%s apply_krylov_dot" % t)
+                    assert torch.equal(y, le.MatMultKrylov(dev(uu))), "%s: MatMultKrylovDot's product differs from MatMultKrylov's" % t
+                    res["%s_dot_%s_y" % (t, name)], res["%s_dot_%s_pw" % (t, name)], res["%s_dot_%s_formy" % (t, name)] = host(y), np.asarray([d]), np.asarray(form)
+                    gen = form[1] if form[0] == 1 else 0
+                    for zero in (0, 1):
+                        x0 = lambda: torch.zeros_like(dev(bb)) if zero else dev(uu)
+                        if gen >= 2:
+                            xo, d = le.smooth_dot(0, dev(bb), x0(), 2, bool(zero))
+                            form = le.last_op_form()
+                            check(form, expect, "%s smooth_dot" % t)
+                            assert torch.equal(xo, le.smooth(0, dev(bb), x0(), 2, bool(zero))), "%s: smooth_dot's iterate differs from smooth's" % t
+                            k = "%s_dot_%s_z%d" % (t, name, zero)
+                            res[k + "_x"], res[k + "_bx"], res[k + "_form"] = host(xo), np.asarray([d]), np.asarray(form)
+                        else:       # no fused b . x_out on this kernel: an error, not a silent number
+                            try:
+                                le.smooth_dot(0, dev(bb), x0(), 2, bool(zero))
+                            except tp.TopOptError as err:
+                                assert err.code == 2, err
+                            else:
+                                raise AssertionError("%s: smooth_dot on a kernel without the fused dot returned a value" % t)
+            le.close()
+            grid.close()
+    res["gen"] = np.asarray([gen])
+
+
+def coarse_steps(expect, res, lvl1):
+    for m, ((ex, ey, ez), nlv) in enumerate(COARSE_MESHES):
+        nx, ny, nz, h = ex + 1, ey + 1, ez + 1, 1.0 / ey
+        rng = np.random.default_rng(700 + m)
+        grid = tp.Grid(nx, ny, nz, h)
+        le = tp.LinearElasticity(grid, tp.SolverOptions(nlvls=nlv))
+        le.SetUpLoadAndBC()
+        tag = "c%d" % m
+        res[tag + "_N"], res[tag + "_KE"], res[tag + "_kf"] = host(le.N), le.KE, le.KE_effective()
+        for kind in rw.GENERATORS:
+            x = rw.design(kind, ex, ey, ez, 2 * int(os.environ.get("TP_MACRO_KZ", "2")))
+            le.AssembleStiffnessMatrix(dev(x), 1e-9, 1.0, 3.0)
+            t = "%s_%s" % (tag, kind)
+            res[t + "_x"] = x
+            for l in range(nlv):
+                n = 3 * le.level_nodes(l)
+                u, b = rng.standard_normal(n), rng.standard_normal(n)
+                res["%s_u%d" % (t, l)], res["%s_b%d" % (t, l)] = u, b
+                e = ["1", "*", "*", "*"] if l == 0 else (lvl1 if l == 1 else expect)
+                tl = "%s_l%d" % (t, l)
+                sweeps(le, l, b, u, rw.STEP_KS, res, tl)        # (last: k = 3 from u, separate launches on every level)
+                check(le.last_op_form(), e[:3], "%s level %d Chebyshev step" % (t, l))
+                if l == nlv - 1:
+                    sweeps(le, l, b, u, (rw.STEP_K_COARSEST,), res, tl)
+                res[tl + "_dinv"] = host(le.level_dinv(l))
+                res[tl + "_lam"] = np.asarray([le.level_lambda(l), le.level_lambda_min(l)])
+                res[tl + "_resid"] = host(le.level_residual(l, dev(b), dev(u)))
+                form = le.last_op_form()
+                check(form, e, "%s level %d residual" % (t, l))
+                res[tl + "_formr"] = np.asarray(form)
+        le.close()
+        grid.close()
+
+
 def cone_filter(expect, res):
     want = dict((int(a), int(b)) for a, b in (p.split(":") for p in expect))
     ex, ey, ez = rw.FILTER_MESH
@@ -168,6 +281,10 @@ if __name__ == "__main__":
         cone_filter(expect, res)
     elif mode == "fine":
         fine(expect, res)
+    elif mode == "fine_steps":
+        fine_steps(expect, res)
+    elif mode == "coarse_steps":
+        coarse_steps(expect, res, sys.argv[4].split(","))
     else:
         coarse(expect, res, sys.argv[4].split(","), int(sys.argv[5]))
     np.savez(out, **res)

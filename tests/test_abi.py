@@ -84,6 +84,7 @@ SWITCHES_SET_BY_NAME = {
     "tests/test_gpu_rowwise.py": ["TP_FINE_V", "TP_FINE_SHAPE", "TP_TILE_KZ", "TP_NO_TILE", "TP_NO_MACRO", "TP_NO_CORR_FUSE", "TP_DIA_SPLIT",
                                   "TP_DIA_NODE", "TP_NO_DIA_SYM", "TP_MACRO_KZ", "TP_FILTER_ZMULTI", "TP_NO_FILTER_TILE"],
     "tests/rowwise_worker.py": ["TP_MACRO_KZ"],
+    "tests/test_gpu_cg_fusions.py": ["TP_NO_FUSE_FIRST", "TP_NO_CG_FUSE", "TP_NO_SPEC_HEAD", "TP_NO_FUSE_RZ", "TP_CG_NT"],
     "tests/test_gpu_pde_rowwise.py": ["TP_NO_PDE_STENCIL"],
     "tests/mp_gloo_worker.py": ["TP_OVERLAP", "TP_TEST_FORCE_GIVEUP", "TP_FINE_V", "TP_FINE_SHAPE"],
     "tools/fine_ab.py": ["TP_FINE_V", "TP_TILE_KZ"],

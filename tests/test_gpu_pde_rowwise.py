@@ -196,20 +196,63 @@ def report(form):
     print("ACHIEVED", form, {k[1]: "%.3g of %g" % v for k, v in sorted(ACHIEVED.items()) if k[0] == form})
 
 
+_WORK = {}
+
+
+def worker_once(tmp_path_factory, form):
+    """one subprocess per form, shared by the test functions that compare its outputs"""
+    if form not in _WORK:
+        env, expect = FORMS[form]
+        out = str(tmp_path_factory.mktemp("pde") / "out.npz")
+        e = dict(os.environ)
+        e.pop("TP_NO_PDE_STENCIL", None)
+        e.update(env)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "pde_rowwise_worker.py"), "single", expect, out], env=e, cwd=ROOT,
+                           capture_output=True, text=True, timeout=280)
+        assert r.returncode == 0, r.stdout[-1500:] + "\n" + r.stderr[-3000:]
+        d = np.load(out)
+        _WORK[form] = {k: d[k] for k in d.files}
+    return _WORK[form]
+
+
 @pytest.mark.parametrize("form", list(FORMS))
-def test_pde_hierarchy_rowwise(tmp_path, orc, arb, form):
-    env, expect = FORMS[form]
-    out = str(tmp_path / "out.npz")
-    e = dict(os.environ)
-    e.pop("TP_NO_PDE_STENCIL", None)
-    e.update(env)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "pde_rowwise_worker.py"), "single", expect, out], env=e, cwd=ROOT,
-                       capture_output=True, text=True, timeout=280)
-    assert r.returncode == 0, r.stdout[-1500:] + "\n" + r.stderr[-3000:]
-    d = np.load(out)
+def test_pde_hierarchy_rowwise(tmp_path_factory, orc, arb, form):
+    d = worker_once(tmp_path_factory, form)
     for m, case in enumerate(rw.PDE_CASES):
         for r_ in range(len(case[3])):
             compare_case(form, lambda name: d["m%d_r%d_%s" % (m, r_, name)], orc, arb, m, r_)
+    report(form)
+
+
+@pytest.mark.parametrize("form", list(FORMS))
+def test_pde_later_steps_rowwise(tmp_path_factory, orc, arb, form):
+    """steps 2 and 3 of a sweep from the zero guess and from a non-zero guess on every level (the stored direction d), each
+    against the step formed in 80-bit arithmetic from the device's own x_{k-1}, x_{k-2}, dinv and window (rw.c_pde_smooth_k)"""
+    d = worker_once(tmp_path_factory, form)
+    for m, case in enumerate(rw.PDE_CASES[:rw.PDE_STEP_CASES]):
+        (ex, ey, ez), _, nlv, ratios = case
+        nx, ny, nz = ex + 1, ey + 1, ez + 1
+        for r_ in range(len(ratios)):
+            get = lambda name: d["m%d_r%d_%s" % (m, r_, name)]
+            ref = reference(orc, arb, (m, r_), (nx, ny, nz), nlv, get("kf"))
+            lab = "%s mesh %s box %s rmin/h %g: " % (form, (ex, ey, ez), rw.pde_box(case), ratios[r_])
+            for l in range(nlv):
+                dims = rw.level_dims(nx, ny, nz, l)
+                inp = rw.pde_inputs(dims, rw.pde_seed(m, r_, l))
+                u, b = inp["normal"], inp["b"]
+                dinv, (lam, lam_min) = get("dinv%d" % l), get("lam%d" % l)
+                theta = ref.theta(l, lam, lam_min)
+                delta = 1.1 * lam - theta
+                c = rw.c_pde_smooth_k(l)
+                for zero in (1, 0):
+                    xs = lambda j: (np.zeros_like(u) if zero else u) if j == 0 else get("l%d_z%d_x%d" % (l, zero, j))
+                    for k in rw.STEP_KS:
+                        c1, c2 = rw.cheb_coeffs(theta, delta, k)
+                        x1, x2 = xs(k - 1), xs(k - 2)
+                        xa = rw.step_k_ref(x1, x2, c1, c2, dinv, b, ref.amg.apply(l, ld(x1)))
+                        sc = rw.scale_smooth_k(ref.scale(l, x1), dinv, c1, c2, b, x1, x2)
+                        note(form, "step 2, 3 %s level %d" % ("zero" if zero else "non-zero", l),
+                             rw.assert_rowwise(xs(k), xa, sc, c, {"dims": dims, "dof": 1, "label": lab + "level %d Chebyshev step %d zero %d" % (l, k, zero)}), c)
     report(form)
 
 

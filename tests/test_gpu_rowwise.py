@@ -6,7 +6,11 @@ both boundary conditions (cantilever: unmasked tiles; scattered Dirichlet dofs: 
 ASSERTS that the forced form is the one that launched (LinearElasticity.last_op_form: generation, tile shape, z-chunk;
 stencil split, node / row form, mirrored reads) and dumps inputs and outputs; this file compares.  References: the arbiter on
 the matrix the kernels apply (KE_effective for apply and the Chebyshev step, KE_krylov for apply_krylov, both as the library
-exports them, hi + lo); the Chebyshev step formed in 80-bit arithmetic from the device's own dinv and window.
+exports them, hi + lo); the Chebyshev step formed in 80-bit arithmetic from the device's own dinv and window.  Three more
+test functions share a second worker run per form (modes fine_steps / coarse_steps): steps 2 and 3 of a sweep (20 on the
+coarsest level), the residual epilogue through LinearElasticity.level_residual, and the VALUES of the fused dot products
+(MatMultKrylovDot, smooth_dot) -- ownership of the seam nodes and the summation, on the seeded field and on a field of void
+rows only.
 
 Bounds (c, in units of eps x row scale) and the worst c the kernels ACHIEVED on the MI355X (recorded for the reader; the
 bounds come from the operation counts and the oracle's own CPU figures in tests/rowwise.py, not from these):
@@ -25,6 +29,18 @@ bounds come from the operation counts and the oracle's own CPU figures in tests/
     stored stencil, levels 2, 3: split 9; 3 node / row, mirrored / plain; 1
         apply                                     256, 512    4.6; 5.2; 6.0
         diagonal / steps                   256 / 256, 512    40.9 / 2.7, 3.8
+    later Chebyshev steps (step k from the device's own x_{k-1}, x_{k-2}; rw.STEP_MESHES on level 0, rw.COARSE_MESHES above), the
+    residual epilogue b - A x, and the values of the fused dot products (against the 80-bit sum of the device's own vectors, in
+    units of eps x sum |terms|; bound: the power of two above the chain 3 kz + 20 + ceil(workgroups / 256), rw.c_dot)
+        fine gen 2 / 3 / auto: steps 2, 3 zero / non-zero   128    1.9 / 1.9   (gen 1: 1.9 / 2.0; per-node: 1.3 / 2.0;
+                                                                                level 0 of the coarse meshes: 1.9 / 2.3)
+        fine, every form: residual                           64    1.0         (per-node: 1.1)
+        u . A u (EPI_APPLY_DOT), every fine form        32, 128    2.4         (32 x 8 tiles, kz 23: 2.1 of 128; per-node 1.7)
+        b . x_out (EPI_CHEB_DOT), generations 2 and 3    32, 128    2.1
+        level 1 from the fine densities: steps / residual   256    1.7, 1.5 / 5.5
+        level 1 stored, split 9 / 3 / 1: steps / residual   256    1.4, 1.6 / 7.9, 6.8, 8.1
+        stencil, levels 2, 3: steps 2, 3 / residual    256, 512    2.5, 2.5 / 7.7
+        coarsest level, step 20 zero (one-launch run) / non-zero    512    1.0 / 1.6
     restrict / prolong_add (every level pair)       64 / 64    4.1 / 2.9
     dfdx on a converged state (rtol 1e-5)              128    2.2
     cone filter, Hs / forward / gradients, the same for the tiled, z-multi, wide, ring and generic kernels
@@ -209,6 +225,158 @@ def test_coarse_levels_transfers_and_dfdx_rowwise(tmp_path, orc, arb, form):
                 _, _, dfa, _ = arb.compliance_sens(nx, ny, nz, ld(KE), ld(U), ld(x))
                 note(form, "dfdx", rw.assert_rowwise(d[t + "_df"], dfa, rw.scale_dfdx(nx, ny, nz, KE, U, x), rw.C_DFDX,
                                                      {"dims": (ex, ey, ez), "dof": 0, "label": lab + "dfdx"}), rw.C_DFDX)
+    print("ACHIEVED", form, {k[1]: "%.3g of %g" % v for k, v in ACHIEVED.items() if k[0] == form})
+
+
+# =====================================================================================================================
+# later Chebyshev steps, the residual epilogue, the values of the fused dot products (rw.STEP_MESHES, rw.COARSE_MESHES)
+# =====================================================================================================================
+_WORK = {}
+
+
+def worker_once(tmp_path_factory, mode, form, env, *args):
+    """one subprocess per form and mode, shared by the test functions that compare its outputs"""
+    if (mode, form) not in _WORK:
+        d = run_worker(tmp_path_factory.mktemp(mode), mode, env, *args)
+        _WORK[(mode, form)] = {k: d[k] for k in d.files}
+    return _WORK[(mode, form)]
+
+
+def window(l, nlv, lam, lam_min):
+    lmin = lam_min if (l == nlv - 1 and l > 0) else 0.1 * lam
+    return 0.5 * (1.1 * lam + lmin), 0.5 * (1.1 * lam - lmin)
+
+
+def check_later_steps(form, what, get, l, nlv, ks, b, u, A, S, where, lab):
+    """step k of the sweeps from the zero guess and from u, for k in ks: the device's x_k against the step formed in 80-bit
+    arithmetic from its own x_{k-1}, x_{k-2}, dinv and window.  A(v): the arbiter's product, S(v): the row scale S_l(|v|), both
+    cached by the bits of v (forms that produce the same iterates share them)"""
+    dinv, (lam, lam_min) = get("dinv"), get("lam")
+    theta, delta = window(l, nlv, float(lam), float(lam_min))
+    c = rw.c_smooth_k(l)
+    for zero in (1, 0):
+        xs = lambda j: (np.zeros_like(u) if zero else u) if j == 0 else get("z%d_x%d" % (zero, j))
+        for k in ks:
+            c1, c2 = rw.cheb_coeffs(theta, delta, k)
+            x1, x2 = xs(k - 1), xs(k - 2)
+            xa = rw.step_k_ref(x1, x2, c1, c2, dinv, b, A(x1))
+            sc = rw.scale_smooth_k(S(x1), dinv, c1, c2, b, x1, x2)
+            note(form, "%sstep %s %s" % (what, "2, 3" if k <= 3 else k, "zero" if zero else "non-zero"),
+                 rw.assert_rowwise(xs(k), xa, sc, c, dict(where, label=lab + "Chebyshev step %d of a sweep from %s" % (k, "the zero guess" if zero else "u"))), c)
+
+
+def fine_case_refs(orc, arb, d, form, m, scattered):
+    ex, ey, ez = rw.STEP_MESHES[m]
+    nx, ny, nz = ex + 1, ey + 1, ez + 1
+    tag = "m%d_s%d" % (m, scattered)
+    N, KE = d[tag + "_N"], d[tag + "_KE"]
+    kf = d[tag + "_kf"] if form != "per_node" else ld(KE)
+    return (ex, ey, ez), (nx, ny, nz), tag, N, KE, kf
+
+
+def fine_ops(orc, arb, dims, KE, kf, E, N, key):
+    nx, ny, nz = dims
+    A = lambda v: cached(key + ("A", hash(v.tobytes())), lambda: arb.matfree_apply(nx, ny, nz, 3, ld(kf), ld(E), ld(N), ld(v)))
+    S = lambda v: cached(key + ("S", hash(v.tobytes())), lambda: rw.scale_fine(orc, nx, ny, nz, KE, E, v, N))
+    return A, S
+
+
+@pytest.mark.parametrize("form", list(FINE_FORMS))
+def test_fine_later_steps_and_residual_rowwise(tmp_path_factory, orc, arb, form):
+    """steps 2 and 3 of a sweep (the three-term form: load_prev, prev_zero) and r = b - A x through EPI_RESID, row by row"""
+    env, expect = FINE_FORMS[form]
+    d = worker_once(tmp_path_factory, "fine_steps", form, env, expect)
+    for m in range(len(rw.STEP_MESHES)):
+        for scattered in (0, 1):
+            mesh, dims, tag, N, KE, kf = fine_case_refs(orc, arb, d, form, m, scattered)
+            u, b = d[tag + "_u"], d[tag + "_b"]
+            for kind in rw.GENERATORS:
+                t = "%s_%s" % (tag, kind)
+                x = d[t + "_x"]
+                E = orc.simp(x)
+                A, S = fine_ops(orc, arb, dims, KE, kf, E, N, ("steps", m, scattered, form == "per_node", hash(x.tobytes())))
+                lab = "%s mesh %s %s %s: " % (form, mesh, "scattered" if scattered else "cantilever", kind)
+                check_later_steps(form, "", lambda name: d[t + "_" + name], 0, 1, rw.STEP_KS, b, u, A, S,
+                                  {"dims": dims, "kz": int(d[t + "_formk"][3])}, lab)
+                note(form, "residual", rw.assert_rowwise(d[t + "_resid"], ld(b) - A(u), np.abs(b) + S(u), rw.c_resid(0),
+                                                         {"dims": dims, "kz": int(d[t + "_formr"][3]), "label": lab + "residual"}), rw.c_resid(0))
+    print("ACHIEVED", form, {k[1]: "%.3g of %g" % v for k, v in ACHIEVED.items() if k[0] == form})
+
+
+@pytest.mark.parametrize("form", list(FINE_FORMS))
+def test_fine_fused_dot_values(tmp_path_factory, orc, arb, form):
+    """p . A p of EPI_APPLY_DOT (every form) and b . x_out of EPI_CHEB_DOT (generations 2, 3) against the sums formed in 80-bit
+    arithmetic from the device's own vectors: who owns a seam node, and the summation.  Two inputs: the seeded fields, and the
+    same set to zero wherever the row's scale exceeds 1e-6 of the largest -- void terms only, where a node counted twice or not
+    at all is a whole term and not 1e-9 of one.  (The worker asserts the vectors bit-equal to MatMultKrylov's and smooth's.)"""
+    env, expect = FINE_FORMS[form]
+    d = worker_once(tmp_path_factory, "fine_steps", form, env, expect)
+    gen = int(d["gen"][0])
+    assert gen >= 2 or form in ("gen1", "per_node"), (form, gen)       # every other form carries the fused b . x_out
+    for m in range(len(rw.STEP_MESHES)):
+        for scattered in (0, 1):
+            mesh, dims, tag, N, KE, kf = fine_case_refs(orc, arb, d, form, m, scattered)
+            for kind in rw.GENERATORS:
+                for name in ("n", "v"):
+                    t = "%s_%s_dot_%s" % (tag, kind, name)
+                    lab = "%s mesh %s %s %s input %s: " % (form, mesh, "scattered" if scattered else "cantilever", kind, name)
+                    pairs = [("u . A u", d[t + "_u"], d[t + "_y"], float(d[t + "_pw"][0]), d[t + "_formy"])]
+                    if gen >= 2:
+                        pairs += [("b . x_out, zero guess %d" % z, d[t + "_b"], d["%s_z%d_x" % (t, z)], float(d["%s_z%d_bx" % (t, z)][0]),
+                                   d["%s_z%d_form" % (t, z)]) for z in (0, 1)]
+                    for what, a, v, got, f in pairs:
+                        terms = ld(a) * ld(v)
+                        ref, size = terms.sum(), float(np.abs(terms).sum())
+                        kz, nwg = (int(f[3]) if int(f[0]) == 1 else 1), rw.dot_workgroups(f, dims)
+                        c = rw.c_dot(kz, nwg)
+                        assert np.isfinite(got), (lab, what)
+                        # rows that touch void elements only exist on every design but one_void (there the sum is an exact 0)
+                        assert np.count_nonzero(terms) >= (3 if (name == "n" or kind != "one_void") else 0), (lab, what)
+                        err = float(abs(np.longdouble(got) - ref))
+                        print("%s%s: got %.17g, |got - ref| = %.3e = %.3g eps sum|terms|, bound %d (kz %d, %d workgroups)" % (lab, what, got, err, err / (rw.EPS * max(size, 1e-300)), c, kz, nwg))
+                        assert err <= c * rw.EPS * size, "%s%s: |got - ref| = %.3e > %d eps sum|terms| = %.3e (kz %d, %d workgroups)" % (lab, what, err, c, c * rw.EPS * size, kz, nwg)
+                        note(form, "dot " + what.split(",")[0], err / (rw.EPS * max(size, 1e-300)), c)
+    print("ACHIEVED", form, {k[1]: "%.3g of %g" % v for k, v in ACHIEVED.items() if k[0] == form})
+
+
+@pytest.mark.parametrize("form", list(COARSE_FORMS))
+def test_coarse_later_steps_and_residual_rowwise(tmp_path_factory, orc, arb, form):
+    """steps 2 and 3 of a sweep on every level (the stored direction d), step 20 on the coarsest level (from the zero guess: the
+    one-launch run), and the residual epilogue of every level"""
+    env, expect, lvl1, _ = COARSE_FORMS[form]
+    d = worker_once(tmp_path_factory, "coarse_steps", form, env, expect, lvl1)
+    for m, ((ex, ey, ez), nlv) in enumerate(COARSE_MESHES):
+        nx, ny, nz = ex + 1, ey + 1, ez + 1
+        tag = "c%d" % m
+        N, KE, kf = d[tag + "_N"], d[tag + "_KE"], d[tag + "_kf"]
+        for kind in rw.GENERATORS:
+            t = "%s_%s" % (tag, kind)
+            x = d[t + "_x"]
+            E = orc.simp(x)
+
+            def hier():
+                mg, amg = orc.MG(nx, ny, nz, 3, nlv), arb.MG(nx, ny, nz, 3, nlv)
+                mg.assemble(KE, E, N)
+                amg.assemble(ld(KE), ld(E), ld(N))
+                return mg, amg
+            xk = hash(x.tobytes())
+            mg, amg = cached(("hier", m, kind, xk), hier)
+            lab = "%s mesh %s %d levels %s: " % (form, (ex, ey, ez), nlv, kind)
+            for l in range(nlv):
+                dims = rw.level_dims(nx, ny, nz, l)
+                u, b = d["%s_u%d" % (t, l)], d["%s_b%d" % (t, l)]
+                if l == 0:
+                    A, S = fine_ops(orc, arb, (nx, ny, nz), KE, kf, E, N, ("steps0", m, xk))
+                else:
+                    A = lambda v: cached(("A", m, xk, l, hash(v.tobytes())), lambda: amg.apply(l, ld(v)))
+                    S = lambda v: cached(("S", m, xk, l, hash(v.tobytes())), lambda: rw.scale_level(orc, mg, l, (nx, ny, nz), KE, E, N, v))
+                f = tuple(int(v) for v in d["%s_l%d_formr" % (t, l)])
+                w = {"dims": dims, "kz": f[3] if f[0] in (1, 2) else 0}
+                name = "level 0 " if l == 0 else ("level1 " if l == 1 else "stencil ")
+                ks = rw.STEP_KS + ((rw.STEP_K_COARSEST,) if l == nlv - 1 else ())
+                check_later_steps(form, name, lambda q: d["%s_l%d_%s" % (t, l, q)], l, nlv, ks, b, u, A, S, w, lab + "level %d form %s " % (l, f))
+                note(form, name + "residual", rw.assert_rowwise(d["%s_l%d_resid" % (t, l)], ld(b) - A(u), np.abs(b) + S(u), rw.c_resid(l),
+                                                                dict(w, label=lab + "level %d residual, form %s" % (l, f))), rw.c_resid(l))
     print("ACHIEVED", form, {k[1]: "%.3g of %g" % v for k, v in ACHIEVED.items() if k[0] == form})
 
 

@@ -1,7 +1,9 @@
 """The yardstick of tests/test_gpu_rowwise.py held on the CPU: on every 0/1 generator of tests/rowwise.py, on two meshes, the
 float64 oracle stays within a QUARTER of the row-wise bound the HIP kernels are held to -- every level of a 3-level hierarchy,
-the transfers, the Jacobi diagonal, one Chebyshev step, dfdx and the cone filter, each against the 80-bit arbiter.  And the helper itself: an error
-planted where the stiffness is small passes the suite's older metric rel() and fails assert_rowwise.
+the transfers, the Jacobi diagonal, one Chebyshev step, steps 2, 3, 4 (and 20 on the coarsest level) of a sweep, the V-cycle's
+residual, dfdx and the cone filter, each against the 80-bit arbiter.  And the helper itself: an error
+planted where the stiffness is small passes the suite's older metric rel() and fails assert_rowwise; so does a later Chebyshev
+step whose c1 term is dropped on the rows of small scale.
 
 The same for the Helmholtz (PDE) filter's scalar hierarchy (tests/test_gpu_pde_rowwise.py): the oracle within a quarter of each
 constant on every mesh, regime and input of rw.PDE_CASES, and two planted errors in a numpy restatement of the 27 x 27 class
@@ -81,6 +83,24 @@ def test_oracle_within_a_quarter_of_every_bound(orc, arb, kind, mesh):
             sc = rw.scale_smooth(0.0 if zero else sl, dinv, 1.0 / theta, b, x0)
             note("smooth", rw.assert_rowwise(mg.smooth(l, b, x0, 1, zero), xa, sc, rw.c_smooth(l) / 4,
                                              {"label": "oracle Chebyshev step level %d zero %d %s %s" % (l, zero, kind, mesh), "dims": dims}))
+        # ---- the V-cycle's residual b - A x, and step k of a sweep from the oracle's own x_{k-1}, x_{k-2} (rw.c_smooth_k)
+        sb = np.abs(b) + sl
+        note("resid%d" % l, rw.assert_rowwise(b - mg.apply(l, u), ld(b) - ya, sb, rw.c_resid(l) / 4,
+                                              {"label": "oracle residual level %d %s %s" % (l, kind, mesh), "dims": dims}))
+        delta = 0.5 * (1.1 * lam - lmin)
+        for zero in (True, False):
+            x0 = np.zeros(n) if zero else u
+            xs = {0: x0}
+            for k in (2, 3, 4) + ((20,) if l == NLV - 1 else ()):
+                for j in (k - 2, k - 1, k):
+                    if j not in xs:
+                        xs[j] = mg.smooth(l, b, x0, j, zero)
+                c1, c2 = rw.cheb_coeffs(theta, delta, k)
+                x1, x2 = xs[k - 1], xs[k - 2]
+                xa = rw.step_k_ref(x1, x2, c1, c2, dinv, b, amg.apply(l, ld(x1)))
+                sc = rw.scale_smooth_k(rw.scale_level(orc, mg, l, (nx, ny, nz), KE, E, N, x1), dinv, c1, c2, b, x1, x2)
+                note("smooth_k%d" % l, rw.assert_rowwise(xs[k], xa, sc, rw.c_smooth_k(l) / 4,
+                                                         {"label": "oracle Chebyshev step %d level %d zero %d %s %s" % (k, l, zero, kind, mesh), "dims": dims}))
         if l + 1 < NLV:
             rf, xc = rng.standard_normal(n), rng.standard_normal(mg.size(l + 1))
             note("restrict", rw.assert_rowwise(mg.restrict(l, rf), amg.restrict(l, ld(rf)), rw.scale_restrict(mg, l, rf), rw.C_RESTRICT / 4,
@@ -143,6 +163,46 @@ def test_planted_error_passes_rel_and_fails_rowwise(orc, arb):
         rw.assert_rowwise(bad, ya, s, rw.C_FINE, w)
 
 
+def test_planted_step_error_passes_rel_and_fails_rowwise(orc, arb):
+    """step 7 of a sweep from the zero guess (the longest sweep test_chebyshev_smoother runs), restated in numpy (float64) from
+    the oracle's x_6 and x_5 on 31 x 17 x 9 elements, blocks + checkerboard: it holds the row-wise bound.  With the c1 term dropped
+    on every row whose scale is below 1e-6 of the largest it still passes rel() <= 1e-10 and fails the row-wise assertion.
+    Which rows those are: dinv ~ 1 / E, so under a right-hand side of one size the VOID rows carry iterates 1e9 times larger
+    than the rows that touch a solid element, and rel() measures everything against them; the rows of small scale are the
+    4923 that touch solid material.  (The same error planted into step 2 measures 5.8e-10 under rel(): E_void / E_solid = 2e-9
+    times c1 = 0.53; the direction shrinks from step to step, 8e-11 at step 7.)"""
+    ex, ey, ez, k = 31, 17, 9, 7
+    nx, ny, nz, h = ex + 1, ey + 1, ez + 1, 1.0 / ey
+    x = np.maximum(rw.design("blocks", ex, ey, ez), rw.design("checker", ex, ey, ez))
+    KE = orc.hex8_ke_box(h, h, h, 0.3)
+    N, _ = orc.cantilever_bc(nx, ny, nz, h)
+    E = orc.simp(x)
+    mg, amg = orc.MG(nx, ny, nz, 3, 1), arb.MG(nx, ny, nz, 3, 1)
+    mg.assemble(KE, E, N)
+    amg.assemble(ld(KE), ld(E), ld(N))
+    b = np.random.default_rng(1).standard_normal(3 * nx * ny * nz)
+    lam = mg.lam(0)
+    theta, delta = 0.5 * (1.1 * lam + 0.1 * lam), 0.5 * (1.1 * lam - 0.1 * lam)
+    c1, c2 = rw.cheb_coeffs(theta, delta, k)
+    dinv = 1.0 / mg.diag(0)
+    x1, x2 = mg.smooth(0, b, np.zeros_like(b), k - 1, True), mg.smooth(0, b, np.zeros_like(b), k - 2, True)
+    Ax1 = mg.apply(0, x1)
+    step = lambda c1_rows: x1 + (c1_rows * (x1 - x2) + c2 * (dinv * (b - Ax1)))
+    xa = rw.step_k_ref(x1, x2, c1, c2, dinv, b, amg.apply(0, ld(x1)))
+    sc = rw.scale_smooth_k(rw.scale_fine(orc, nx, ny, nz, KE, E, x1, N), dinv, c1, c2, b, x1, x2)
+    w = {"label": "planted step", "dims": (nx, ny, nz)}
+    good = step(c1)
+    assert rw.assert_rowwise(good, xa, sc, rw.c_smooth_k(0) / 4, w) <= 8.0
+    assert rw.rel(good, mg.smooth(0, b, np.zeros_like(b), k, True)) <= 1e-14          # the restatement is the oracle's step
+    small = sc < 1e-6 * sc.max()
+    assert small.sum() > 1000 and (~small).sum() > 1000
+    bad = step(np.where(small, 0.0, c1))
+    assert rw.rel(bad, good) <= 1e-10 and rw.rel(bad, np.asarray(xa, dtype=np.float64)) <= 1e-10
+    with pytest.raises(AssertionError, match=r"rows beyond %g eps scale" % rw.c_smooth_k(0)):
+        rw.assert_rowwise(bad, xa, sc, rw.c_smooth_k(0), w)
+    assert rw.achieved(bad, xa, sc) >= 1e6
+
+
 # =====================================================================================================================
 # the Helmholtz (PDE) filter's scalar hierarchy
 # =====================================================================================================================
@@ -184,6 +244,20 @@ def test_pde_oracle_within_a_quarter_of_every_bound(orc, arb, m):
                 sc = rw.scale_smooth(0.0 if zero else sl, dinv, 1.0 / theta, b, x0)
                 note("pde smooth %d" % l, rw.assert_rowwise(mg.smooth(l, b, x0, 1, zero), xa, sc, rw.c_pde_smooth(l) / 4,
                                                      dict(w, label=lab + "level %d Chebyshev step zero %d" % (l, zero))))
+            delta = theta - (mg.lam_min(l) if (l == nlv - 1 and l > 0) else 0.1 * mg.lam(l))
+            for zero in (True, False):
+                x0 = np.zeros_like(u) if zero else u
+                xs = {0: x0}
+                for k in (2, 3):
+                    for j in (k - 1, k):
+                        if j not in xs:
+                            xs[j] = mg.smooth(l, b, x0, j, zero)
+                    c1, c2 = rw.cheb_coeffs(theta, delta, k)
+                    x1, x2 = xs[k - 1], xs[k - 2]
+                    xa = rw.step_k_ref(x1, x2, c1, c2, dinv, b, amg.apply(l, ld(x1)))
+                    sc = rw.scale_smooth_k(ref.scale(l, x1), dinv, c1, c2, b, x1, x2)
+                    note("pde smooth_k %d" % l, rw.assert_rowwise(xs[k], xa, sc, rw.c_pde_smooth_k(l) / 4,
+                                                           dict(w, label=lab + "level %d Chebyshev step %d zero %d" % (l, k, zero))))
             if l + 1 < nlv:
                 cd = rw.level_dims(nx, ny, nz, l + 1)
                 xc = rw.pde_inputs(cd, rw.pde_seed(m, r, l + 1))

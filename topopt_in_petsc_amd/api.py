@@ -422,6 +422,13 @@ class LinearElasticity:
         _chk(self.L.tp_elasticity_apply_krylov(self.handle, _ptr(u), _ptr(y)), "tp_elasticity_apply_krylov")
         return y
 
+    def MatMultKrylovDot(self, u, y=None):
+        """MatMultKrylov that also returns the value of the product's fused dot product: (y, u . y) -- CG's p . A p"""
+        y = torch.zeros_like(u) if y is None else y
+        d = C.c_double()
+        _chk(self.L.tp_elasticity_apply_krylov_dot(self.handle, _ptr(u), _ptr(y), C.byref(d)), "tp_elasticity_apply_krylov_dot")
+        return y, d.value
+
     # ---- self-weight: a body force that moves with the material ----
     def SetBodyForce(self, b, x_low=0.1):
         """b = (b_x, b_y, b_z), the body force per unit volume at full density (rho g); below x_low the mass is damped as
@@ -667,6 +674,18 @@ class LinearElasticity:
     def smooth(self, l, b, x, k, zero_guess=False):
         _chk(self.L.tp_elasticity_smooth(self.handle, l, _ptr(b), _ptr(x), k, int(zero_guess)), "tp_elasticity_smooth")
         return x
+
+    def smooth_dot(self, l, b, x, k, zero_guess=False):
+        """smooth() whose last step is the fused form that also returns b . x_out (CG's r . z): (x, dot)"""
+        d = C.c_double()
+        _chk(self.L.tp_elasticity_smooth_dot(self.handle, l, _ptr(b), _ptr(x), k, int(zero_guess), C.byref(d)), "tp_elasticity_smooth_dot")
+        return x, d.value
+
+    def level_residual(self, l, b, x):
+        """r = b - A_l x through the residual epilogue of the level's kernel, as the V-cycle forms it"""
+        r = torch.zeros_like(x)
+        _chk(self.L.tp_elasticity_level_residual(self.handle, l, _ptr(b), _ptr(x), _ptr(r)), "tp_elasticity_level_residual")
+        return r
 
     def restrict(self, l, rf):
         rc = self.level_vec(l + 1)

@@ -1193,6 +1193,13 @@ extern "C" int tp_elasticity_apply_krylov(tp_elasticity *e, const double *u, dou
     if (!e || !e->assembled) return TP_ERR_STATE;
     return e->mg.apply_krylov(const_cast<double *>(u), y);
 }
+// ... and the value of its fused dot product, *dot = u . y (all ranks): CG's p . A p, which the call above discards
+extern "C" int tp_elasticity_apply_krylov_dot(tp_elasticity *e, const double *u, double *y, double *dot) {
+    if (!e || !e->assembled) return TP_ERR_STATE;
+    if (!dot) return TP_ERR_ARG;
+    TP_TRY(e->mg.apply_krylov(const_cast<double *>(u), y));
+    return read_scal(e->grid, S_PW, 1, dot);
+}
 
 __global__ __launch_bounds__(BLK) void k_mul(double *__restrict__ y, const double *__restrict__ a,
                                              const double *__restrict__ b, long n) {
@@ -1360,6 +1367,35 @@ extern "C" int tp_elasticity_smooth(tp_elasticity *e, int l, const double *b, do
     TP_TRY(e->mg.drain_halos());
     TP_HIP(hipMemcpyAsync(x, L.x, nb, hipMemcpyDeviceToDevice, e->grid->stream));
     return TP_OK;
+}
+// smooth() with a dot slot: the last step is the fused EPI_CHEB_DOT and *dot = b . x_out (all ranks).  TP_ERR_STATE where the
+// level's kernel carries no fused dot; TP_ERR_ARG where no operator step would run (k < 1, or the zero guess with k < 2).
+extern "C" int tp_elasticity_smooth_dot(tp_elasticity *e, int l, const double *b, double *x, int k, int zero_guess, double *dot) {
+    if (!e || !e->assembled || l < 0 || l >= e->mg.nlv) return TP_ERR_STATE;
+    if (!b || !x || !dot || k < (zero_guess ? 2 : 1)) return TP_ERR_ARG;
+    MGSolver<3> &mg = e->mg;
+    if (mg.fine_generation(mg.lv[l]) < 2) return TP_ERR_STATE;  // as op<EPI_CHEB_DOT> would say, before anything is launched
+    Level<3> &L = mg.lv[l];
+    const size_t nb = sizeof(double) * (size_t)L.ndof();
+    if (!zero_guess) TP_HIP(hipMemcpyAsync(L.x, x, nb, hipMemcpyDeviceToDevice, e->grid->stream));
+    TP_TRY(mg.smooth(l, b, k, zero_guess != 0, S_TMP));
+    TP_TRY(finish_tail<1>(e->grid, mg.last_nblocks, S_TMP));
+    TP_TRY(mg.drain_halos());
+    TP_HIP(hipMemcpyAsync(x, L.x, nb, hipMemcpyDeviceToDevice, e->grid->stream));
+    return read_scal(e->grid, S_TMP, 1, dot);
+}
+// r = b - A_l x through the residual epilogue of the level's kernel, as the V-cycle forms it (ghost planes of x refreshed first)
+extern "C" int tp_elasticity_level_residual(tp_elasticity *e, int l, const double *b, const double *x, double *r) {
+    if (!e || !e->assembled || l < 0 || l >= e->mg.nlv) return TP_ERR_STATE;
+    if (!b || !x || !r) return TP_ERR_ARG;
+    MGSolver<3> &mg = e->mg;
+    TP_TRY(mg.halo(l, const_cast<double *>(x)));
+    NodeArgs a{};
+    a.x = x;
+    a.out = r;
+    a.b = b;
+    TP_TRY(mg.op<EPI_RESID>(l, a));
+    return mg.drain_halos();
 }
 extern "C" int tp_elasticity_restrict(tp_elasticity *e, int l, const double *rf, double *rc) {
     MGSolver<3> &mg = e->mg;

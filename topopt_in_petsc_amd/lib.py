@@ -99,6 +99,7 @@ SYMBOLS = {
     "tp_elasticity_assemble": (_i, [_vp, _vp, _d, _d, _d]),
     "tp_elasticity_apply": (_i, [_vp, _vp, _vp]),
     "tp_elasticity_apply_krylov": (_i, [_vp, _vp, _vp]),
+    "tp_elasticity_apply_krylov_dot": (_i, [_vp, _vp, _vp, C.POINTER(C.c_double)]),
     "tp_elasticity_solve": (_i, [_vp, _vp, _vp, C.POINTER(_i), C.POINTER(_d), C.POINTER(_d), _vp, _i]),
     "tp_elasticity_objective": (_i, [_vp, _vp, _vp, _d, _d, _d, _d, C.POINTER(_d), C.POINTER(_d), _vp, _vp]),
     "tp_elasticity_objective_only": (_i, [_vp, _vp, _vp, _d, _d, _d, _d, C.POINTER(_d), C.POINTER(_d)]),
@@ -123,6 +124,8 @@ SYMBOLS = {
     "tp_elasticity_level_pc": (_i, [_vp, _i, _i, _vp, _vp]),
     "tp_elasticity_level_gmres": (_i, [_vp, _i, _i, _i, _i, _d, _vp, _vp, _i, C.POINTER(_i)]),
     "tp_elasticity_smooth": (_i, [_vp, _i, _vp, _vp, _i, _i]),
+    "tp_elasticity_smooth_dot": (_i, [_vp, _i, _vp, _vp, _i, _i, C.POINTER(C.c_double)]),
+    "tp_elasticity_level_residual": (_i, [_vp, _i, _vp, _vp, _vp]),
     "tp_elasticity_restrict": (_i, [_vp, _i, _vp, _vp]),
     "tp_elasticity_prolong_add": (_i, [_vp, _i, _vp, _vp]),
     "tp_elasticity_last_stats": (_i, [_vp, C.POINTER(_d), C.POINTER(_d), C.POINTER(_l)]),
