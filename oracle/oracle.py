@@ -74,6 +74,8 @@ def lib():
         L.orc_mg_level_diag.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.orc_mg_level_csr.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.orc_mg_smooth.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        L.orc_mg_coarse_solve.restype = C.c_int
+        L.orc_mg_coarse_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.orc_filter_create.restype = C.c_void_p
         L.orc_filter_create.argtypes = [C.c_int] * 3 + [c_real] * 4
         L.orc_filter_destroy.argtypes = [C.c_void_p]
@@ -305,6 +307,15 @@ class MG:
     def smooth(self, l, b, x, k, zero_guess):
         b, x = f64(b), f64(x).copy()
         self.L.orc_mg_smooth(self.h, l, _p(b), _p(x), k, int(zero_guess))
+        return x
+
+    def coarse_solve(self, b):
+        """x = A^-1 b on the coarsest level by the V-cycle's banded Cholesky factor (set_coarse_direct() before assemble())"""
+        b = f64(b)
+        assert b.size == self.size(self.nlv - 1), (b.size, self.size(self.nlv - 1))
+        x = np.zeros_like(b)
+        if self.L.orc_mg_coarse_solve(self.h, _p(b), _p(x)) != 0:
+            raise RuntimeError("coarse_solve: the last assemble() left no factor (set_coarse_direct, more than one level, positive pivots)")
         return x
 
     def precond(self, r):

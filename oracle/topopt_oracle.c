@@ -679,6 +679,7 @@ typedef struct {
     int coarse_direct;
     long chol_hb;
     double *chol;
+    int chol_ok; /* the factor in chol belongs to the last orc_mg_assemble and every pivot was positive */
     /* diagnostic (round 6): a separate operator for the Krylov method's own products A x0, A p (NULL: A[0]); the
      * preconditioner's fine level stays A[0] */
     csr_t *Akry;
@@ -992,6 +993,7 @@ ORC_API void orc_mg_assemble(orc_mg_t *s, const double *KE, const double *E, con
         s->dinv[l] = NULL;
     }
     s->A[0] = assemble_csr(s->nx[0], s->ny[0], s->nz[0], s->dof, KE, E, N);
+    s->chol_ok = 0;
     for (int l = 0; l + 1 < s->nlv; l++) {
         csr_t *AP = csr_matmul(s->A[l], s->P[l]);
         s->A[l + 1] = csr_matmul(s->PT[l], AP);
@@ -1013,6 +1015,7 @@ ORC_API void orc_mg_assemble(orc_mg_t *s, const double *KE, const double *E, con
         } else if (l == s->nlv - 1 && l > 0 && s->coarse_direct) {
             s->lam[l] = s->lam_min[l] = 1.0; /* not used */
             if (chol_band_factor(s)) s->lam[l] = s->lam_min[l] = NAN;
+            else s->chol_ok = 1;
         } else if (l == s->nlv - 1 && l > 0) {
             /* coarsest level: the Chebyshev iteration there is a SOLVE (the reference uses a Krylov
              * method, LinearElasticity.cc:720-731), so its window spans the whole spectrum:
@@ -1173,6 +1176,13 @@ ORC_API void orc_mg_smooth(orc_mg_t *s, int l, const double *b, double *x, int k
     /* same windows as the V-cycle: the coarsest level spans the whole spectrum */
     double lmin = (l == s->nlv - 1 && l > 0) ? s->lam_min[l] : s->cheb_lo * s->lam[l];
     cheb_smooth(s->A[l], s->dinv[l], b, x, s->r[l], s->d[l], k, lmin, s->cheb_hi * s->lam[l], zero_guess);
+}
+/* x = A^-1 b on the coarsest level by the V-cycle's banded Cholesky factor (orc_mg_set_coarse_direct before the
+ * assembly); returns 0, or -1 where the last assembly left no factor (switch off, one level, non-positive pivot) */
+ORC_API int orc_mg_coarse_solve(orc_mg_t *s, const double *b, double *x) {
+    if (!s->chol_ok || !s->chol) return -1;
+    chol_band_solve(s, b, x);
+    return 0;
 }
 
 /* ------------------------------------------------------------------------- */

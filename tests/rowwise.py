@@ -578,3 +578,145 @@ def assert_rowwise(got, ref_ld, scale, c, where):
                              "scale / max scale = %.1e); %s" % (where.get("label"), int((ratio > c).sum()), ratio.size, c, row, ratio[row],
                                                                 d[row], scale[row], scale[row] / scale.max(), _describe(row, where)))
     return float(ratio[row])
+
+
+# =====================================================================================================================
+# the exact coarse solve (csrc/coarse_direct.h; tests/test_gpu_coarse_direct.py): its admission window as a table, the designs
+# and right-hand sides of its cases, and the distances its result is held to
+# =====================================================================================================================
+CD_NB, CD_KBMAX, CD_MINROWS, CD_MAXROWS, CD_RUN_ROWS = 32, 12, 128, 4096, 448
+
+
+def cd_geom(mesh, nlv):
+    """-> (coarsest node dims, rows, KB, blocks, padding) of the coarsest level of a mesh (elements) with nlv levels: MGSolver's
+    coarse_direct_factor() restated -- half bandwidth 3 (nx ny + nx + 1) + 2 in blocks of 32 rows, rows padded to whole blocks"""
+    ex, ey, ez = mesh
+    cx, cy, cz = level_dims(ex + 1, ey + 1, ez + 1, nlv - 1)
+    rows = 3 * cx * cy * cz
+    KB = (3 * (cx * cy + cx + 1) + 2 + CD_NB - 1) // CD_NB
+    blocks = (rows + CD_NB - 1) // CD_NB
+    return (cx, cy, cz), rows, KB, blocks, blocks * CD_NB - rows
+
+
+def cd_rows(mesh, nlv, coarse_direct):
+    """rows LinearElasticity.coarse_direct_active() must report (0: the Chebyshev run): coarse_direct_ok() restated -- 128 ..
+    4096 rows, 1 .. 12 blocks of band, and below 449 rows (the one-workgroup Chebyshev run) only for coarse_direct = 2"""
+    _, rows, KB, _, _ = cd_geom(mesh, nlv)
+    ok = coarse_direct >= 1 and nlv >= 2 and CD_MINROWS <= rows <= CD_MAXROWS and 1 <= KB <= CD_KBMAX and (coarse_direct >= 2 or rows > CD_RUN_ROWS)
+    return rows if ok else 0
+
+
+# (mesh in elements, levels, rows reported for coarse_direct = 1, for coarse_direct = 2): coarsest nodes, KB, blocks, padding; why
+# KB = 1 needs a coarsest plane of 2 x 2 nodes: 4 x 4 x 48 elements with three levels -- the library accepts the mesh and every
+# level's kernel runs on it, so the table starts at KB = 1.  KB 9 and 10 are the older tests' (tests/test_gpu_parity.py).
+#
+# MEASURED, energy norm of the distance from the arbiter's solve (largest over the six designs, both right-hand sides; the
+# maximum norm stays within a factor of 3 of it everywhere): the float64 oracle's banded Cholesky and the numpy restatement of
+# the device's method on the CPU; the device (MI355X, both inverse forms: they agree to three digits) for the reader -- the
+# bound is 16 x the larger REFERENCE figure of the same design and right-hand side, never the device's own.  Worst ratio of a
+# device distance to its bound over the table: 0.18.  The two inverse forms stand <= 1.1e-10 (energy) / 7.8e-15 (maximum norm)
+# from each other.  Per design, the spread is that of the condition number: checker / blocks 1e-7 .. 5e-5, one_solid 1e-8,
+# one_void, zlayer and synth 1e-15 .. 6e-12 (the floor's regime).
+#     mesh, levels       KB    oracle    numpy W   device        worst design
+#     4x4x48, 3           1    6.7e-14   6.9e-14   6.8e-14       one_solid (every other design: <= 4.3e-15)
+#     8x8x24, 3           2    2.1e-06   2.1e-06   6.8e-07       blocks
+#     12x12x28, 3         3    5.9e-07   5.6e-07   7.2e-07       blocks
+#     28x12x20, 3         4    5.7e-06   4.6e-06   4.3e-06       checker (device: blocks)
+#     20x20x20, 3         5    8.9e-07   1.2e-06   1.0e-06       blocks
+#     28x28x12, 3         7    1.0e-06   8.9e-07   1.7e-06       blocks, checker
+#     28x32x16, 3         8    7.9e-06   6.6e-06   1.1e-06       blocks (device: checker)
+#     36x36x16, 3        11    5.8e-06   4.9e-06   4.1e-06       blocks (device: checker)
+#     36x40x44, 3        12    2.0e-06   2.4e-06   2.3e-07       checker
+#     64x32x32, 4         6    5.1e-05   5.3e-05   1.8e-05       checker
+# The oracle and the numpy restatement stand this close to each other because most of the distance is the float64 rounding of the
+# coarse MATRIX (two or three Galerkin products of moduli nine decades apart), which they share; the explicit inverse adds nothing.
+CD_CASES = [
+    ((4, 4, 48), 3, 0, 156),        # 2x2x13, KB 1, 5 blocks, pad 4: one ring slot; coarse_direct = 2 only
+    ((8, 8, 24), 3, 0, 189),        # 3x3x7, KB 2, 6 blocks, pad 3: ring shorter than the four waves; coarse_direct = 2 only
+    ((12, 12, 28), 3, 0, 384),      # 4x4x8, KB 3, 12 blocks, pad 0; coarse_direct = 2 only
+    ((28, 12, 20), 3, 576, 576),    # 8x4x6, KB 4, 18 blocks, pad 0: no padding, admitted by default
+    ((20, 20, 20), 3, 648, 648),    # 6x6x6, KB 5, 21 blocks, pad 24
+    ((28, 28, 12), 3, 768, 768),    # 8x8x4, KB 7, 24 blocks, pad 0
+    ((28, 32, 16), 3, 1080, 1080),  # 8x9x5, KB 8, 34 blocks, pad 8
+    ((36, 36, 16), 3, 1500, 1500),  # 10x10x5, KB 11, 47 blocks, pad 4
+    ((36, 40, 44), 3, 3960, 3960),  # 10x11x12, KB 12, 124 blocks, pad 8: widest band and most blocks, 7 levels of divide and conquer, ragged last segment
+    ((64, 32, 32), 4, 675, 675),    # 9x5x5, KB 6, 22 blocks, pad 29: four levels, the early factorisation with level 2 beside it
+]
+# rejected whatever the option says: 0 rows, and the solve of coarse_direct = 0 bit for bit
+CD_REJECTED = [
+    ((40, 36, 48), 3),              # 11x10x13: 4290 rows at KB 12, too many rows
+    ((8, 8, 8), 3),                 # 3x3x3: 81 rows, too few
+]
+CD_DESIGNS = ("blocks", "checker", "one_solid", "one_void", "zlayer", "synth")
+CD_SEQUENCE = ("blocks", "checker", "blocks", "checker", "one_solid", "one_void", "zlayer", "synth")      # A, B, A, B, then the rest
+CD_SETUP_CASES = (9, 3)             # indices into CD_CASES: the overlapped set-up against the serial one (the second: every switch alone)
+CD_MARGIN = 16                      # the margin this file gives every measured constant
+# floor of the bound (energy norm, maximum norm): the largest d(oracle) over the one_void designs of CD_CASES, where the matrix is
+# well conditioned -- 5.99e-12 and 8.53e-12, both on the four-level case -- rounded up to a power of two
+CD_FLOOR = (2.0 ** -37, 2.0 ** -36)
+
+
+def cd_design(orc, kind, mesh):
+    ex, ey, ez = mesh
+    return orc.synth_density(ex, ey, ez, 1.0 / ey) if kind == "synth" else design(kind, ex, ey, ez, 4)
+
+
+def cd_rhs(dims, case):
+    """{name: right-hand side} on the coarsest level: a seeded normal field, and one supported on one node -- on ONE of its three
+    dofs, component y of the central node, so that the solution is a single column of the inverse (a load on all three
+    components would be a sum of three columns)"""
+    cx, cy, cz = dims
+    n = 3 * cx * cy * cz
+    e = np.zeros(n)
+    e[3 * (cx // 2 + cx * (cy // 2 + cy * (cz // 2))) + 1] = 1.0
+    return {"normal": np.random.default_rng(4000 + case).standard_normal(n), "unit": e}
+
+
+class CdNorm:
+    """dist(v, x_a) = (energy norm of v - x_a in the arbiter's coarsest matrix relative to x_a's, max|v - x_a| / max|x_a|); the
+    matrix is kept as 80-bit CSR arrays and applied in 80-bit arithmetic"""
+
+    def __init__(self, amg, l):
+        n, nnz = amg.size(l), amg.L.orc_mg_level_nnz(amg.h, l)
+        self.rp, self.ci, self.v = np.zeros(n + 1, dtype=np.int64), np.zeros(nnz, dtype=np.int32), np.zeros(nnz, dtype=np.longdouble)
+        amg.L.orc_mg_level_csr(amg.h, l, self.rp.ctypes.data, self.ci.ctypes.data, self.v.ctypes.data)
+        assert (np.diff(self.rp) > 0).all()
+
+    def energy(self, u):
+        u = np.asarray(u, dtype=np.longdouble)
+        return np.sqrt(np.dot(u, np.add.reduceat(self.v * u[self.ci], self.rp[:-1])))
+
+    def dist(self, v, xa):
+        d = np.asarray(v, dtype=np.longdouble) - xa
+        return float(self.energy(d) / self.energy(xa)), float(np.abs(d).max() / np.abs(xa).max())
+
+
+class CdRef:
+    """The references of one (case, design): the arbiter's coarse_solve on its own Galerkin hierarchy of KE, E, N (80-bit), the
+    float64 oracle's, and the device's METHOD restated in numpy on the oracle's coarse matrix: L = Cholesky, W = L^-1 by
+    triangular solves, x = W^T (W b).  norm: the CdNorm of the arbiter's matrix."""
+
+    def __init__(self, orc, arb, mesh, nlv, KE, E, N):
+        import scipy.linalg as sla
+        ex, ey, ez = mesh
+        L = lambda a: np.ascontiguousarray(a, dtype=np.longdouble)
+        self.mg, self.amg = orc.MG(ex + 1, ey + 1, ez + 1, 3, nlv, 2, 20), arb.MG(ex + 1, ey + 1, ez + 1, 3, nlv, 2, 20)
+        for m, f in ((self.mg, orc.f64), (self.amg, L)):
+            m.set_coarse_direct(True)
+            m.assemble(f(KE), f(E), f(N))
+        self.lc = nlv - 1
+        self.norm = CdNorm(self.amg, self.lc)
+        self.A = self.mg.csr(self.lc)
+        A = self.A.toarray()
+        self.W = sla.solve_triangular(np.linalg.cholesky(A), np.eye(A.shape[0]), lower=True)
+
+    def solves(self, b):
+        """-> (x_a, x_oracle, x_numpy_W)"""
+        return self.amg.coarse_solve(np.ascontiguousarray(b, dtype=np.longdouble)), self.mg.coarse_solve(b), self.W.T @ (self.W @ b)
+
+    def dist(self, v, xa):
+        return self.norm.dist(v, xa)
+
+    def residual(self, b, x):
+        """max|A x - b| / max|b| in float64 with the oracle's coarsest matrix"""
+        return float(np.abs(self.A @ x - b).max() / np.abs(b).max())

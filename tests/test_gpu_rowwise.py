@@ -29,6 +29,8 @@ bounds come from the operation counts and the oracle's own CPU figures in tests/
     stored stencil, levels 2, 3: split 9; 3 node / row, mirrored / plain; 1
         apply                                     256, 512    4.6; 5.2; 6.0
         diagonal / steps                   256 / 256, 512    40.9 / 2.7, 3.8
+    level 2's element matrices by the generic contraction (TP_NO_L2_FAST) / the fast one on 7 workgroups (TP_L2_BLOCKS=7)
+        apply / diagonal / steps            256, 512 / 256 / 256, 512    4.6 / 34.3, 40.9 / 2.7, 3.1 and 2.6, 3.5
     later Chebyshev steps (step k from the device's own x_{k-1}, x_{k-2}; rw.STEP_MESHES on level 0, rw.COARSE_MESHES above), the
     residual epilogue b - A x, and the values of the fused dot products (against the 80-bit sum of the device's own vectors, in
     units of eps x sum |terms|; bound: the power of two above the chain 3 kz + 20 + ceil(workgroups / 256), rw.c_dot)
@@ -66,7 +68,7 @@ pytestmark = pytest.mark.gpu
 FINE_MESHES, COARSE_MESHES = rw.FINE_MESHES, rw.COARSE_MESHES
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SWITCHES = ("TP_FINE_V", "TP_FINE_SHAPE", "TP_TILE_KZ", "TP_NO_TILE", "TP_NO_MACRO", "TP_NO_CORR_FUSE", "TP_DIA_SPLIT", "TP_DIA_NODE",
-            "TP_NO_DIA_SYM", "TP_MACRO_KZ")
+            "TP_NO_DIA_SYM", "TP_MACRO_KZ", "TP_NO_L2_FAST", "TP_L2_BLOCKS")
 
 # form -> (environment, expected last_op_form)
 FINE_FORMS = {
@@ -89,7 +91,12 @@ COARSE_FORMS = {
     "stencil_split3_row_mirrored": ({"TP_NO_MACRO": "1", "TP_DIA_SPLIT": "3", "TP_DIA_NODE": "0"}, "4,3,0,1", "4,3,0,1", 0),
     "stencil_split3_row_plain": ({"TP_NO_MACRO": "1", "TP_DIA_SPLIT": "3", "TP_DIA_NODE": "0", "TP_NO_DIA_SYM": "1"}, "4,3,0,0", "4,3,0,0", 0),
     "stencil_split1": ({"TP_NO_MACRO": "1", "TP_DIA_SPLIT": "1"}, "4,1,0,0", "4,1,0,0", 0),
+    # level 2's Galerkin contraction in its other forms (elasticity_setup_from_E): every element through the generic
+    # contraction, and the fast one as a grid stride of few workgroups -- the operators are the default job's
+    "level2_generic_contraction": ({"TP_NO_L2_FAST": "1"}, "4,*,*,*", "2,1,0,*", 0),
+    "level2_fast_contraction_7_workgroups": ({"TP_L2_BLOCKS": "7"}, "4,*,*,*", "2,1,0,*", 0),
 }
+L2_FORMS = {"level2_generic_contraction": False, "level2_fast_contraction_7_workgroups": True}    # form -> bit-equal to the default job
 ACHIEVED = {}
 _REF = {}
 
@@ -377,6 +384,22 @@ def test_coarse_later_steps_and_residual_rowwise(tmp_path_factory, orc, arb, for
                 check_later_steps(form, name, lambda q: d["%s_l%d_%s" % (t, l, q)], l, nlv, ks, b, u, A, S, w, lab + "level %d form %s " % (l, f))
                 note(form, name + "residual", rw.assert_rowwise(d["%s_l%d_resid" % (t, l)], ld(b) - A(u), np.abs(b) + S(u), rw.c_resid(l),
                                                                 dict(w, label=lab + "level %d residual, form %s" % (l, f))), rw.c_resid(l))
+    if form in L2_FORMS:
+        # did the latched switch take effect?  Against the default job's dump (same inputs, same worker): the generic contraction
+        # sums level 2's element matrices in another order -- its Jacobi diagonals on the levels >= 2 are NOT all the default's
+        # bits; k_galerkin_l2_fast forms an element with the same arithmetic whichever workgroup takes it, so 7 workgroups must
+        # reproduce EVERY bit of the default job (an element left out or formed twice by the stride would show here; that the
+        # stride ran is visible in no result, by construction)
+        env0, expect0, lvl10, _ = COARSE_FORMS["level1_from_fine_fused_corr"]
+        d0 = worker_once(tmp_path_factory, "coarse_steps", "level1_from_fine_fused_corr", env0, expect0, lvl10)
+        assert sorted(d0) == sorted(d)
+        differ = [k for k in sorted(d) if not (d0[k].shape == d[k].shape and np.array_equal(d0[k], d[k]))]
+        print("L2 form %s: %d of %d dumped arrays differ from the default job's bits" % (form, len(differ), len(d)))
+        if L2_FORMS[form]:
+            assert not differ, differ[:8]
+        else:
+            assert any(k.endswith("_l2_dinv") for k in differ), differ[:8]
+            assert not [k for k in differ if "_l0_" in k or "_l1_" in k], "levels 0 and 1 do not depend on level 2's contraction"
     print("ACHIEVED", form, {k[1]: "%.3g of %g" % v for k, v in ACHIEVED.items() if k[0] == form})
 
 

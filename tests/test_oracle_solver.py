@@ -421,6 +421,56 @@ def test_exact_coarse_solve_equals_sparse_lu(orc, nlv, cycles):
     assert its_d <= its_c + 1 and np.abs(U_d - U_c).max() <= 1e-4 * np.abs(U_c).max()
 
 
+@pytest.mark.parametrize("flavour", ["f64", "ld"])
+def test_coarse_solve_entry_point_against_sparse_lu(orc, flavour):
+    """MG.coarse_solve(b): the V-cycle's banded Cholesky solve of the coarsest level as an entry point of its own
+    (orc_mg_coarse_solve), oracle and arbiter, against scipy's sparse LU of MG.csr(lc) on the 16 x 8 x 8 mesh.  Bounds: a
+    backward-stable solve of an SPD system leaves ||b - A x||_2 <= c n u ||A||_2 ||x||_2 and stands within c n u cond_2(A) of
+    another such solve, u the unit round-off of the flavour (2^-53, 2^-64; the LU itself is a float64 solve: the distance from it
+    is held at 2^-53 for both), c = 4.  Without a factor -- switch off, or one level -- it is an error, not a number."""
+    from oracle import arbiter as arb
+    m = orc if flavour == "f64" else arb
+    nx, ny, nz, h, KE, N, b, x, E = _problem(orc, 16, 8, 8, "synth")
+    nlv, lc = 3, 2
+    mg = m.MG(nx, ny, nz, 3, nlv, 2, 20)
+    mg.assemble(m.f64(KE), m.f64(E), m.f64(N))
+    rng = np.random.default_rng(11)
+    n = mg.size(lc)
+    rhs = rng.standard_normal(n)
+    with pytest.raises(RuntimeError):
+        mg.coarse_solve(rhs)                 # no factor: coarse_direct is off
+    mg.set_coarse_direct(True)
+    mg.assemble(m.f64(KE), m.f64(E), m.f64(N))
+    xs = mg.coarse_solve(rhs)
+    assert xs.dtype == m.REAL and xs.shape == (n,)
+    A = orc.MG.csr(mg, lc) if flavour == "f64" else None
+    if A is None:       # the arbiter's matrix, rounded to float64 for scipy (a relative perturbation of 2^-53 per entry)
+        import scipy.sparse as sp
+        from tests.rowwise import CdNorm
+        nrm = CdNorm(mg, lc)
+        A = sp.csr_matrix((nrm.v.astype(np.float64), nrm.ci, nrm.rp), shape=(n, n))
+        r = m.f64(rhs) - np.add.reduceat(nrm.v * xs[nrm.ci], nrm.rp[:-1])      # residual in 80-bit arithmetic
+    else:
+        r = rhs - A @ xs
+    Ad = A.toarray()
+    assert np.array_equal(Ad, Ad.T) or np.abs(Ad - Ad.T).max() <= 1e-15 * np.abs(Ad).max()
+    ev = np.linalg.eigvalsh(0.5 * (Ad + Ad.T))
+    assert ev[0] > 0
+    u = 2.0 ** -53 if flavour == "f64" else 2.0 ** -64
+    resid = float(np.sqrt(np.dot(r, r)) / (ev[-1] * np.sqrt(np.dot(xs, xs))))
+    x_lu = spla.splu(A.tocsc()).solve(rhs)
+    err = float(np.abs(np.asarray(xs, dtype=np.float64) - x_lu).max() / np.abs(x_lu).max())
+    print("coarse_solve %s: n %d cond %.2e residual %.2e (bound %.2e) distance from LU %.2e (bound %.2e)"
+          % (flavour, n, ev[-1] / ev[0], resid, 4 * n * u, err, 4 * n * 2.0 ** -53 * ev[-1] / ev[0]))
+    assert resid <= 4 * n * u
+    assert err <= 4 * n * 2.0 ** -53 * ev[-1] / ev[0]
+    one = m.MG(nx, ny, nz, 3, 1)
+    one.set_coarse_direct(True)
+    one.assemble(m.f64(KE), m.f64(E), m.f64(N))
+    with pytest.raises(RuntimeError):
+        one.coarse_solve(np.zeros(one.size(0)))
+
+
 def test_arbiter_is_the_same_algorithm_in_extended_precision():
     """oracle/arbiter.py: topopt_oracle.c rebuilt with `long double` for `double`.  Same inputs -> the same iteration count, a
     residual history and a compliance that agree with the double-precision oracle to rounding (1e-11 on a 10^4-DOF mesh), and

@@ -333,3 +333,39 @@ def test_pde_planted_table_errors(orc, arb):
     with pytest.raises(AssertionError, match=r"node \(0, 0, \d+\)"):
         rw.assert_rowwise(rw.pde_table_apply(bad[1], dims, u), ref.amg.apply(1, ld(u)), ref.scale(1, u), rw.c_pde_level(1),
                           {"dims": dims, "dof": 1, "label": "one weight of level 1 off by 2^-40"})
+
+
+# =====================================================================================================================
+# the admission window of the exact coarse solve as a table (tests/test_gpu_coarse_direct.py)
+# =====================================================================================================================
+def test_coarse_direct_geometry_table():
+    """rw.cd_geom / rw.cd_rows reproduce the figures the table was written from, the window's edges, and the geometries the
+    older tests reach (tests/test_gpu_parity.py: KB 6, 9, 10)"""
+    want = {((4, 4, 48), 3): ((2, 2, 13), 156, 1, 5, 4), ((8, 8, 24), 3): ((3, 3, 7), 189, 2, 6, 3), ((12, 12, 28), 3): ((4, 4, 8), 384, 3, 12, 0),
+            ((28, 12, 20), 3): ((8, 4, 6), 576, 4, 18, 0), ((20, 20, 20), 3): ((6, 6, 6), 648, 5, 21, 24), ((28, 28, 12), 3): ((8, 8, 4), 768, 7, 24, 0),
+            ((28, 32, 16), 3): ((8, 9, 5), 1080, 8, 34, 8), ((36, 36, 16), 3): ((10, 10, 5), 1500, 11, 47, 4),
+            ((36, 40, 44), 3): ((10, 11, 12), 3960, 12, 124, 8), ((64, 32, 32), 4): ((9, 5, 5), 675, 6, 22, 29)}
+    assert [(c[0], c[1]) for c in rw.CD_CASES] == list(want)
+    for mesh, nlv, rows1, rows2 in rw.CD_CASES:
+        assert rw.cd_geom(mesh, nlv) == want[(mesh, nlv)], (mesh, rw.cd_geom(mesh, nlv))
+        rows = want[(mesh, nlv)][1]
+        assert rows2 == rows == rw.cd_rows(mesh, nlv, 2) and rows1 == rw.cd_rows(mesh, nlv, 1) == (rows if rows > 448 else 0)
+        assert rw.cd_rows(mesh, nlv, 0) == 0
+    # every band width 1 .. 12, a padded and an unpadded last block, more than 69 blocks, three cases below 449 rows
+    assert sorted({rw.cd_geom(c[0], c[1])[2] for c in rw.CD_CASES}) == [1, 2, 3, 4, 5, 6, 7, 8, 11, 12]
+    assert {rw.cd_geom(c[0], c[1])[4] == 0 for c in rw.CD_CASES} == {True, False}
+    assert max(rw.cd_geom(c[0], c[1])[3] for c in rw.CD_CASES) == 124 and sum(c[2] == 0 for c in rw.CD_CASES) == 3
+    # rejected: too many rows (at an admissible band), too few rows
+    assert rw.cd_geom((40, 36, 48), 3)[1:3] == (4290, 12) and rw.cd_geom((8, 8, 8), 3)[1] == 81
+    assert all(rw.cd_rows(m, n, cd) == 0 for m, n in rw.CD_REJECTED for cd in (1, 2))
+    # the band too wide (test_coarsest_level_too_wide_for_the_exact_solve_falls_back): 11 x 11 x 7 nodes, 13 blocks
+    assert rw.cd_geom((40, 40, 24), 3)[2] == 13 and rw.cd_rows((40, 40, 24), 3, 2) == 0
+    # the older tests' geometries: test_coarsest_level_solved_exactly and test_exact_coarse_solve_inverse_forms_agree
+    old = [((64, 32, 32), 4), ((48, 24, 24), 3), ((64, 64, 64), 4), ((24, 40, 24), 3), ((32, 32, 32), 3)]
+    geo = [rw.cd_geom(m, n) for m, n in old]
+    assert sorted({g[2] for g in geo}) == [6, 9, 10] and sorted({g[4] for g in geo}) == [9, 15, 21, 29]
+    assert min(g[3] for g in geo) == 22 and max(g[3] for g in geo) == 69
+    assert all(rw.cd_rows(m, n, 1) == g[1] for (m, n), g in zip(old, geo))
+    # the design sequence of the stale-data test: A, B, A, B first, and every design once after that
+    assert rw.CD_SEQUENCE[:4] == ("blocks", "checker", "blocks", "checker") and set(rw.CD_SEQUENCE) == set(rw.CD_DESIGNS)
+    assert rw.CD_CASES[rw.CD_SETUP_CASES[0]][:2] == ((64, 32, 32), 4) and rw.CD_CASES[rw.CD_SETUP_CASES[1]][:2] == ((28, 12, 20), 3)
