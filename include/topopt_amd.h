@@ -162,6 +162,10 @@ int tp_rccl_selftest(int device, void *stream, long n, double *max_err);
 int tp_set_device(int device);             /* hipSetDevice: before tp_malloc of the tp_comm staging buffers */
 int tp_malloc(void **p, size_t bytes);
 int tp_free(void *p);
+/* bytes of device memory the library's own objects (grids, solvers, filters, ... and their work space) hold in this process
+ * right now.  Memory from tp_malloc is the caller's and is not counted.  Destroying every object brings it back to 0: a
+ * test of ownership reads it before a create and after the destroy. */
+long long tp_device_bytes_live(void);
 int tp_memcpy_h2d(void *dst, const void *src, size_t bytes);
 int tp_memcpy_d2h(void *dst, const void *src, size_t bytes);
 int tp_sync(const tp_grid *g);

@@ -68,6 +68,14 @@ def test_only_switches_h_reads_the_environment():
     assert readers == ["switches.h"], readers
 
 
+def test_only_common_h_allocates_device_memory():
+    """device memory has one owner type, DevBuf of csrc/common.h, and the two raw helpers behind tp_malloc / tp_free beside it; no
+    other file there allocates or frees any"""
+    users = sorted(f for f in os.listdir(CSRC)
+                   if any(call in open(os.path.join(CSRC, f)).read() for call in ("hipMalloc(", "hipFree(")))
+    assert users == ["common.h"], users
+
+
 # The library switches that bench.py, tests/*.py and tools/*.py put into the environment of a process that loads the
 # library, by the file that sets them.  An explicit list: TP_BENCH_*, TP_CHECK_OUT, TP_ERR_*, TP_LIB, TP_RANK, ... are not
 # library switches.  A name added to one of these files belongs here as well; a name may leave this list only with the

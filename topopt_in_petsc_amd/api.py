@@ -30,6 +30,11 @@ def _chk(code, where):
         raise TopOptError(code, where)
 
 
+def device_bytes_live():
+    """bytes of device memory the library's own objects hold in this process (torch's tensors and tp_malloc are not counted)"""
+    return int(_lib.load_library().tp_device_bytes_live())
+
+
 def check_body_force(b, x_low):
     """-> ((b_x, b_y, b_z), x_low) as floats; ValueError unless b is three finite numbers and 0 <= x_low < 1"""
     import math

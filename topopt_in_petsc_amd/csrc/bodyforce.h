@@ -117,7 +117,7 @@ extern "C" int tp_elasticity_body_load(tp_elasticity *e, const double *xPhys, co
     body_par(b3, x_low, g, &p);
     const long lay = (long)q.ex * q.ey, nown = q.owned_nodes();
     if (g->has_comm) {  // the ghost element layer above <- the upper neighbour's first own layer, as tp_elasticity_assemble fills d_E
-        if (!e->d_xg) TP_HIP(hipMalloc((void **)&e->d_xg, sizeof(double) * (size_t)lay));
+        if (!e->d_xg) TP_TRY(e->d_xg.alloc((size_t)lay));
         TP_TRY(exchange_segments(g, xPhys, nullptr, nullptr, e->d_xg, lay, 1, lay));
     }
     TP_LAUNCH(k_body_load, dim3((int)((nown + BLK - 1) / BLK)), dim3(BLK), 0, g->stream, q, p, xPhys, (const double *)e->d_xg, rhs_base, rhs);

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -42,6 +43,66 @@ inline int tp_launch_check(const char *what) {
         int lrc_ = tp_launch_check(#kernel);              \
         if (lrc_) return lrc_;                            \
     } while (0)
+
+// ---------------------------------------------------------------------------
+// Device memory has one owner type.  DevBuf<T> frees what it holds when it dies or is given new contents, converts to T *
+// where a kernel or a copy wants the address, and keeps the bytes alive in all DevBufs of the process in one counter
+// (tp_device_bytes_live), so that a test can see a leak.  Memory handed to the caller through tp_malloc / tp_free is the
+// caller's: it goes through the two raw helpers and is not counted.  Nothing else in csrc allocates or frees device memory.
+// ---------------------------------------------------------------------------
+inline std::atomic<long long> &dev_bytes_live() {
+    static std::atomic<long long> v{0};
+    return v;
+}
+inline hipError_t dev_raw_malloc(void **p, size_t bytes) { return hipMalloc(p, bytes); }
+inline hipError_t dev_raw_free(void *p) { return hipFree(p); }
+template <class T>
+struct DevBuf {
+    T *p = nullptr;
+    size_t n = 0;  // elements
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr, o.n = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept {
+        if (this != &o) {
+            reset();
+            p = o.p, n = o.n;
+            o.p = nullptr, o.n = 0;
+        }
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+    void reset() {
+        if (p) {
+            (void)hipFree(p);
+            dev_bytes_live() -= (long long)(sizeof(T) * n);
+        }
+        p = nullptr, n = 0;
+    }
+    // count elements, previous contents freed first
+    int alloc(size_t count) {
+        reset();
+        TP_HIP(hipMalloc((void **)&p, sizeof(T) * count));
+        if (p) n = count, dev_bytes_live() += (long long)(sizeof(T) * n);
+        return TP_OK;
+    }
+    // ... zero-filled: on a stream, or before the call returns
+    int alloc_zero(size_t count, hipStream_t s) {
+        TP_TRY(alloc(count));
+        TP_HIP(hipMemsetAsync(p, 0, sizeof(T) * count, s));
+        return TP_OK;
+    }
+    int alloc_zero(size_t count) {
+        TP_TRY(alloc(count));
+        TP_HIP(hipMemset(p, 0, sizeof(T) * count));
+        return TP_OK;
+    }
+    operator T *() const { return p; }
+};
+// waits for the stream on every way out of a scope: declared AFTER the local DevBufs that work on the stream still uses
+struct StreamSyncAtExit {
+    hipStream_t s;
+    ~StreamSyncAtExit() { (void)hipStreamSynchronize(s); }
+};
 
 constexpr int WAVE = 64;     // CDNA wavefront
 constexpr int BLK  = 256;    // default workgroup: 4 waves, one per SIMD

@@ -349,11 +349,11 @@ struct tp_filter {
     int type, conn;
     double R;
     long nel, lay;
-    double *wtab, *Hs, *xg, *tmp;
+    DevBuf<double> wtab, Hs, xg, tmp;
     // PDE filter
-    MGSolver<1> *pde;
+    std::unique_ptr<MGSolver<1>> pde;
     std::vector<double> KF;  // per level 64
-    double *d_KF, *d_wtab = nullptr, *xe, *rhs, *u;
+    DevBuf<double> d_KF, d_wtab, xe, rhs, u;
     double elemVol;
     int last_its;
     double last_rnorm;
@@ -602,15 +602,13 @@ extern "C" int tp_filter_mult_h(tp_filter *f, const double *x, double *y) {
 }
 extern "C" int tp_filter_create(tp_filter **out, tp_grid *g, int filterType, double rmin, const tp_solver_opts *po) {
     if (!out || !g) return TP_ERR_ARG;
-    tp_filter *f = new tp_filter();
+    std::unique_ptr<tp_filter> f(new tp_filter());
     f->grid = g;
     f->type = filterType;
     f->R = rmin;
     f->conn = 0;
     f->nel = (long)g->ex * g->ey * g->ez_own;
     f->lay = (long)g->ex * g->ey;
-    f->wtab = f->Hs = f->xg = f->tmp = f->d_KF = f->xe = f->rhs = f->u = nullptr;
-    f->pde = nullptr;
     f->last_its = 0;
     f->last_rnorm = 0.0;
     f->violations = 0;
@@ -620,10 +618,7 @@ extern "C" int tp_filter_create(tp_filter **out, tp_grid *g, int filterType, dou
         int conn = (int)fmax(ceil(rmin / dx) - 1, fmax(ceil(rmin / dy) - 1, ceil(rmin / dz) - 1));
         conn = std::min(conn, std::min(g->ex / 2, std::min(g->ey / 2, g->ez_glob / 2)));
         if (conn < 0) conn = 0;
-        if (g->nranks > 1 && conn > g->ez_own) {
-            delete f;
-            return TP_ERR_ARG;
-        }
+        if (g->nranks > 1 && conn > g->ez_own) return TP_ERR_ARG;
         f->conn = conn;
         const int w1 = 2 * conn + 1;
         std::vector<double> w((size_t)w1 * w1 * w1);
@@ -633,15 +628,15 @@ extern "C" int tp_filter_create(tp_filter **out, tp_grid *g, int filterType, dou
                     double dist = sqrt((di * dx) * (di * dx) + (dj * dy) * (dj * dy) + (dk * dz) * (dk * dz));
                     w[((size_t)(dk + conn) * w1 + (dj + conn)) * w1 + (di + conn)] = dist < rmin ? rmin - dist : 0.0;  // strict, :430
                 }
-        TP_HIP(hipMalloc((void **)&f->wtab, sizeof(double) * w.size()));
+        TP_TRY(f->wtab.alloc(w.size()));
         TP_HIP(hipMemcpy(f->wtab, w.data(), sizeof(double) * w.size(), hipMemcpyHostToDevice));
-        TP_HIP(hipMalloc((void **)&f->Hs, sizeof(double) * (size_t)f->nel));
-        TP_HIP(hipMalloc((void **)&f->tmp, sizeof(double) * (size_t)f->nel));
+        TP_TRY(f->Hs.alloc((size_t)f->nel));
+        TP_TRY(f->tmp.alloc((size_t)f->nel));
         const size_t ng = (size_t)(g->ez_own + 2 * conn) * f->lay;
-        TP_HIP(hipMalloc((void **)&f->xg, sizeof(double) * ng));
+        TP_TRY(f->xg.alloc(ng));
         // Hs = H * 1 (:445-448)
         TP_LAUNCH(k_set, dim3(grid_for((long)ng)), dim3(BLK), 0, g->stream, f->xg, 1.0, (long)ng);
-        TP_TRY(filter_conv(f, f->Hs, nullptr, nullptr));
+        TP_TRY(filter_conv(f.get(), f->Hs, nullptr, nullptr));
     } else if (filterType == 2) {
         tp_solver_opts o;
         if (po) {
@@ -656,8 +651,10 @@ extern "C" int tp_filter_create(tp_filter **out, tp_grid *g, int filterType, dou
             o.ncoarse = 10;    // :357
         }
         const int fdiv = 1 << (o.nlvls - 1);
-        if (g->ex % fdiv || g->ey % fdiv || g->ez_own % fdiv) {
-            delete f;
+        if (g->ex % fdiv || g->ey % fdiv || g->ez_own % fdiv) return TP_ERR_ARG;
+        if (o.ksp_mode != 0 && o.ksp_mode != 1) return TP_ERR_ARG;
+        if (o.ksp_mode == 1 && g->has_comm) {
+            fprintf(stderr, "topopt_amd: ksp_mode 1 (the reference's FGMRES / GMRES configuration) runs on one device only\n");
             return TP_ERR_ARG;
         }
         f->elemVol = dx * dy * dz;
@@ -675,15 +672,15 @@ extern "C" int tp_filter_create(tp_filter **out, tp_grid *g, int filterType, dou
                                 s += W[(c * 8 + a) * 8 + I] * f->KF[(size_t)64 * (l - 1) + 8 * a + b] * W[(c * 8 + b) * 8 + J];
                     f->KF[(size_t)64 * l + 8 * I + J] = s;
                 }
-        TP_HIP(hipMalloc((void **)&f->d_KF, sizeof(double) * f->KF.size()));
+        TP_TRY(f->d_KF.alloc(f->KF.size()));
         TP_HIP(hipMemcpy(f->d_KF, f->KF.data(), sizeof(double) * f->KF.size(), hipMemcpyHostToDevice));
         {   // the levels' operators as 27-point stencils (operators.h: ScalarStencilOp): one 27 x 27 table per level
             std::vector<double> Wt((size_t)729 * o.nlvls);
             for (int l = 0; l < o.nlvls; l++) pde_stencil_table(f->KF.data() + (size_t)64 * l, Wt.data() + (size_t)729 * l);
-            TP_HIP(hipMalloc((void **)&f->d_wtab, sizeof(double) * Wt.size()));
+            TP_TRY(f->d_wtab.alloc(Wt.size()));
             TP_HIP(hipMemcpy(f->d_wtab, Wt.data(), sizeof(double) * Wt.size(), hipMemcpyHostToDevice));
         }
-        f->pde = new MGSolver<1>();
+        f->pde.reset(new MGSolver<1>());
         MGSolver<1> &mg = *f->pde;
         mg.grid = g;
         mg.nlv = o.nlvls;
@@ -696,35 +693,21 @@ extern "C" int tp_filter_create(tp_filter **out, tp_grid *g, int filterType, dou
             L.wtab = f->d_wtab + 729 * l;
             L.E = nullptr;
             L.mask = nullptr;
-            L.S = L.Kel = nullptr;
             TP_TRY(mg.setup_matfree_level(l, f->KF.data()));
         }
         mg.ready = true;
-        if (o.ksp_mode != 0 && o.ksp_mode != 1) return TP_ERR_ARG;
-        if (o.ksp_mode == 1 && g->has_comm) {
-            fprintf(stderr, "topopt_amd: ksp_mode 1 (the reference's FGMRES / GMRES configuration) runs on one device only\n");
-            return TP_ERR_ARG;
-        }
         if (o.ksp_mode == 0) TP_TRY(mg.estimate_spectra(1));
         Geom q = mg.lv[0].g;
-        TP_HIP(hipMalloc((void **)&f->xe, sizeof(double) * (size_t)q.elems_stored()));
-        TP_HIP(hipMalloc((void **)&f->rhs, sizeof(double) * (size_t)q.nodes()));
-        TP_HIP(hipMalloc((void **)&f->u, sizeof(double) * (size_t)q.nodes()));
-        TP_HIP(hipMemset(f->u, 0, sizeof(double) * (size_t)q.nodes()));
-        TP_HIP(hipMemset(f->rhs, 0, sizeof(double) * (size_t)q.nodes()));
-        TP_HIP(hipMemset(f->xe, 0, sizeof(double) * (size_t)q.elems_stored()));
+        TP_TRY(f->xe.alloc_zero((size_t)q.elems_stored()));
+        TP_TRY(f->rhs.alloc_zero((size_t)q.nodes()));
+        TP_TRY(f->u.alloc_zero((size_t)q.nodes()));
     }
-    *out = f;
+    *out = f.release();
     return TP_OK;
 }
 extern "C" int tp_filter_destroy(tp_filter *f) {
     if (!f) return TP_OK;
     (void)hipStreamSynchronize(f->grid->stream);
-    for (double *p : {f->wtab, f->Hs, f->xg, f->tmp, f->d_KF, f->d_wtab, f->xe, f->rhs, f->u}) (void)hipFree(p);
-    if (f->pde) {
-        f->pde->free_levels();
-        delete f->pde;
-    }
     delete f;
     return TP_OK;
 }

@@ -20,9 +20,9 @@ struct tp_grid {
     tp_comm comm_host;                // the host framework's hooks given at creation (restored by tp_grid_drop_rccl)
     int ex, ey, ez_glob, ez_own;  // fine level element counts
     int rank, nranks;
-    double *partials;   // [dev] MAX_RED_BLOCKS * 4
-    double *scal;       // [dev] 64 device scalars
-    unsigned *ticket;   // [dev] arrival counter of the in-kernel reduction tails (common.h: reduce_tail), rests at 0
+    DevBuf<double> partials;  // [dev] MAX_RED_BLOCKS * 4
+    DevBuf<double> scal;      // [dev] 64 device scalars
+    DevBuf<unsigned> ticket;  // [dev] arrival counter of the in-kernel reduction tails (common.h: reduce_tail), rests at 0
     double *h_scal;     // pinned host mirror
     double *h_scal_dev; // its address as the device sees it (kernels that deposit a scalar for the host directly)
     hipEvent_t ev_scal; // marks the read-back of read_scal_begin
@@ -42,6 +42,7 @@ struct tp_grid {
     std::vector<hipEvent_t> ct_ev[4];
     double ct_host_s[4] = {0, 0, 0, 0};
     long ct_calls[4] = {0, 0, 0, 0};
+    ~tp_grid();  // (topopt_amd.hip, beside tp_grid_destroy)
 };
 struct CommMark {
     tp_grid *g;

@@ -64,9 +64,9 @@ struct tp_localvol {
     int conn, bpl;
     double R;
     long nel, lay;
-    double *wtab = nullptr, *xg = nullptr, *cnt = nullptr, *rb = nullptr;
-    double *part = nullptr;  // [dev] 2 * bpl * ez_own block partials of k_localvol_pow
-    double *red = nullptr;   // [dev] 2 + ez_own: sum, max, layer sums
+    DevBuf<double> wtab, xg, cnt, rb;
+    DevBuf<double> part;  // [dev] 2 * bpl * ez_own block partials of k_localvol_pow
+    DevBuf<double> red;   // [dev] 2 + ez_own: sum, max, layer sums
     int last_kernel = 0;
 };
 
@@ -85,7 +85,6 @@ static int localvol_fill(tp_localvol *lv, const double *x) {
 extern "C" int tp_localvol_destroy(tp_localvol *lv) {
     if (!lv) return TP_OK;
     (void)hipStreamSynchronize(lv->grid->stream);
-    for (double *p : {lv->wtab, lv->xg, lv->cnt, lv->rb, lv->part, lv->red}) (void)hipFree(p);
     delete lv;
     return TP_OK;
 }
@@ -97,7 +96,7 @@ extern "C" int tp_localvol_create(tp_localvol **out, tp_grid *g, double R) {
     conn = std::min(conn, std::min(g->ex / 2, std::min(g->ey / 2, g->ez_glob / 2)));
     if (conn < 0) conn = 0;
     if (g->nranks > 1 && conn > g->ez_own) return TP_ERR_ARG;
-    tp_localvol *lv = new tp_localvol();
+    std::unique_ptr<tp_localvol> lv(new tp_localvol());
     lv->grid = g;
     lv->R = R;
     lv->conn = conn;
@@ -113,25 +112,17 @@ extern "C" int tp_localvol_create(tp_localvol **out, tp_grid *g, double R) {
                 w[((size_t)(dk + conn) * w1 + (dj + conn)) * w1 + (di + conn)] = dist < R ? 1.0 : 0.0;  // strict, as filter.h
             }
     const size_t ng = (size_t)(g->ez_own + 2 * conn) * lv->lay;
-    int rc = TP_OK;
-    auto body = [&]() -> int {
-        TP_HIP(hipMalloc((void **)&lv->wtab, sizeof(double) * w.size()));
-        TP_HIP(hipMemcpy(lv->wtab, w.data(), sizeof(double) * w.size(), hipMemcpyHostToDevice));
-        TP_HIP(hipMalloc((void **)&lv->xg, sizeof(double) * ng));
-        TP_HIP(hipMalloc((void **)&lv->cnt, sizeof(double) * (size_t)lv->nel));
-        TP_HIP(hipMalloc((void **)&lv->rb, sizeof(double) * (size_t)lv->nel));
-        TP_HIP(hipMalloc((void **)&lv->part, sizeof(double) * 2 * (size_t)lv->bpl * g->ez_own));
-        TP_HIP(hipMalloc((void **)&lv->red, sizeof(double) * (size_t)(2 + g->ez_own)));
-        // cnt = ball_sum(1), the way Hs = H * 1 is made
-        TP_LAUNCH(k_set, dim3(grid_for((long)ng)), dim3(BLK), 0, g->stream, lv->xg, 1.0, (long)ng);
-        return localvol_conv(lv, lv->cnt, nullptr);
-    };
-    rc = body();
-    if (rc) {
-        tp_localvol_destroy(lv);
-        return rc;
-    }
-    *out = lv;
+    TP_TRY(lv->wtab.alloc(w.size()));
+    TP_HIP(hipMemcpy(lv->wtab, w.data(), sizeof(double) * w.size(), hipMemcpyHostToDevice));
+    TP_TRY(lv->xg.alloc(ng));
+    TP_TRY(lv->cnt.alloc((size_t)lv->nel));
+    TP_TRY(lv->rb.alloc((size_t)lv->nel));
+    TP_TRY(lv->part.alloc(2 * (size_t)lv->bpl * g->ez_own));
+    TP_TRY(lv->red.alloc((size_t)(2 + g->ez_own)));
+    // cnt = ball_sum(1), the way Hs = H * 1 is made
+    TP_LAUNCH(k_set, dim3(grid_for((long)ng)), dim3(BLK), 0, g->stream, lv->xg, 1.0, (long)ng);
+    TP_TRY(localvol_conv(lv.get(), lv->cnt, nullptr));
+    *out = lv.release();
     return TP_OK;
 }
 extern "C" int tp_localvol_stencil_width(const tp_localvol *lv) { return lv ? lv->conn : -1; }

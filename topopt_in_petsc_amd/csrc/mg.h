@@ -95,7 +95,13 @@ struct MGSolver {
     bool is_rep(int i) const { return i >= nlv; }
     bool allow_replicate = false;  // set by the owner when the coarsest level is a stored stencil (elasticity)
     tp_solver_opts opt;
-    double *cg_r = nullptr, *cg_p = nullptr, *cg_w = nullptr, *cg_p2 = nullptr;
+    // Storage of every slot's level vectors, stencil and element matrices: lv[i] holds plain views of it (Level is copied and
+    // read by the kernels' argument structs).  alloc_levels allocates the vectors; the owner asks for S and Kel where its
+    // level kind has them.
+    struct LevelStore {
+        DevBuf<double> b, x, x2, r, d, dinv, S, Kel;
+    } store[LV_SLOTS];
+    DevBuf<double> cg_r, cg_p, cg_w, cg_p2;
     bool ready = false;
     int last_nblocks = 0;  // workgroups (= reduction partials) of the last op<EPI_APPLY_DOT>
     // what the last op<>() launched, for the tests (tp_elasticity_last_op_form): [0] 1 fine tile kernel, 2 level 1 from the fine
@@ -128,8 +134,9 @@ struct MGSolver {
     // Lanczos work space per level (kept across design iterations): basis, coefficients, reduction partials, pinned
     // host copy of the coefficients; the runs of different levels are independent and may share the device
     struct LanBuf {
-        double *V = nullptr, *coef = nullptr, *part = nullptr, *hc = nullptr;
-        unsigned *ticket = nullptr, *mticket = nullptr;  // arrival counters of the chain's in-kernel reductions (its own: the chains of the levels run side by side)
+        DevBuf<double> V, coef, part;
+        double *hc = nullptr;
+        DevBuf<unsigned> ticket, mticket;  // arrival counters of the chain's in-kernel reductions (its own: the chains of the levels run side by side)
         size_t cap = 0;
         int m = 0;
     };
@@ -146,14 +153,14 @@ struct MGSolver {
     // assembly -- level 1's chain needs two small kernels, not the stencils of the levels below it.  Valid for one assembly.
     hipEvent_t lv_ready[LV_SLOTS] = {};
     bool lv_ready_set[LV_SLOTS] = {};
-    XcdRunCtrl *lan_ctl = nullptr;      // [dev] control block of the one-XCD Lanczos run
+    DevBuf<XcdRunCtrl> lan_ctl;         // [dev] control block of the one-XCD Lanczos run
     hipStream_t side_stream = nullptr;  // owner's spare stream (idle during estimate_spectra): a second one for the chains
 
     // ---- the coarsest level solved exactly (coarse_direct.h; mg_coarse.h): opt.coarse_direct, one rank or the replicated copy
     struct CoarseDirect {
         CdGeom g{};
-        double *Lb = nullptr, *Tm = nullptr, *Ld = nullptr, *Linv = nullptr, *W = nullptr, *Wt = nullptr, *y = nullptr;
-        XcdRunCtrl *ctl = nullptr;
+        DevBuf<double> Lb, Tm, Ld, Linv, W, Wt, y;
+        DevBuf<XcdRunCtrl> ctl;
         int level = -1;       // the level the factor belongs to (nlv - 1, or nlv: the replicated copy)
         bool factored = false;
     } cd;
@@ -164,8 +171,8 @@ struct MGSolver {
     bool cd_deferred_last = false;  // the last assembly's factorisation ran beside the head of the solve (give-up severity)
 
     // ---- the coarsest level's run in one launch (coarse_run.h; mg_coarse.h)
-    unsigned long long *run_cnt = nullptr;  // [dev] arrival counter (monotone over the runs) + give-up flag
-    XcdRunCtrl *run_ctl = nullptr;          // [dev] control block of the one-XCD run (zero between runs)
+    DevBuf<unsigned long long> run_cnt;     // [dev] arrival counter (monotone over the runs) + give-up flag
+    DevBuf<XcdRunCtrl> run_ctl;             // [dev] control block of the one-XCD run (zero between runs)
     bool gaveup_seen = false;               // the last diverged solve found a give-up flag raised by a one-XCD kernel
     int gaveup_mask = 0;  // which control block raised the flag xcd_gaveup() found: 1 Chebyshev run, 2 Lanczos run, 4 factorisation
     unsigned long long run_base = 0;        // arrivals of all runs so far
@@ -300,7 +307,13 @@ struct MGSolver {
     // mg_cycle.h -- storage, smoother, V-cycle, preconditioned CG
     // =====================================================================================================
     int alloc_levels();
+    // the six vectors of slot i, zeroed on the grid's stream; level i's stencil (`slices` x ndof doubles, zeroed on that stream or before the call returns) and its element matrices
+    int alloc_vectors(int i);
+    int alloc_stencil(int i, int slices, bool on_stream);
+    int alloc_elem_matrices(int i);
+    // graphs, streams, events, pinned memory and the reference solver's work space (device memory dies with its DevBufs)
     void free_levels();
+    ~MGSolver() { free_levels(); }
     // Jacobi diagonal + Chebyshev bound of a matrix-free level
     int setup_matfree_level(int l, const double *h_KE);
     // every rank's owned rows of `nseg` consecutive level vectors -> the replicated global arrays

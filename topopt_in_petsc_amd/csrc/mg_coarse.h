@@ -169,12 +169,6 @@ template <int DOF>
 void MGSolver<DOF>::coarse_direct_free() {
     if (cd_pending && lan_stream[nlv - 1]) (void)hipStreamSynchronize(lan_stream[nlv - 1]);
     cd_pending = false;
-    for (double **p : {&cd.Lb, &cd.Tm, &cd.Ld, &cd.Linv, &cd.W, &cd.Wt, &cd.y}) {
-        (void)hipFree(*p);
-        *p = nullptr;
-    }
-    (void)hipFree(cd.ctl);
-    cd.ctl = nullptr;
     cd.factored = false;
     cd.level = -1;
 }
@@ -193,15 +187,14 @@ int MGSolver<DOF>::coarse_direct_factor(int parts) {
     g.KB = (int)(((long)DOF * (L.g.plane() + L.g.nx + 1) + DOF - 1 + CD_NB - 1) / CD_NB);
     if (cd.level != l || cd.g.np != g.np || cd.g.KB != g.KB) {
         coarse_direct_free();
-        TP_HIP(hipMalloc((void **)&cd.Lb, sizeof(double) * (size_t)g.nblk * (g.KB + 1) * CD_NB * CD_NB));
-        TP_HIP(hipMalloc((void **)&cd.Ld, sizeof(double) * (size_t)g.nblk * CD_NB * CD_NB));
-        TP_HIP(hipMalloc((void **)&cd.Linv, sizeof(double) * (size_t)g.nblk * CD_NB * CD_NB));
-        TP_HIP(hipMalloc((void **)&cd.W, sizeof(double) * (size_t)g.np * g.np));
-        TP_HIP(hipMalloc((void **)&cd.Tm, sizeof(double) * (size_t)g.np * g.np));
-        TP_HIP(hipMalloc((void **)&cd.Wt, sizeof(double) * (size_t)g.np * g.np));
-        TP_HIP(hipMalloc((void **)&cd.y, sizeof(double) * (size_t)g.np));
-        TP_HIP(hipMalloc((void **)&cd.ctl, sizeof(XcdRunCtrl)));
-        TP_HIP(hipMemsetAsync(cd.ctl, 0, sizeof(XcdRunCtrl), s));
+        TP_TRY(cd.Lb.alloc((size_t)g.nblk * (g.KB + 1) * CD_NB * CD_NB));
+        TP_TRY(cd.Ld.alloc((size_t)g.nblk * CD_NB * CD_NB));
+        TP_TRY(cd.Linv.alloc((size_t)g.nblk * CD_NB * CD_NB));
+        TP_TRY(cd.W.alloc((size_t)g.np * g.np));
+        TP_TRY(cd.Tm.alloc((size_t)g.np * g.np));
+        TP_TRY(cd.Wt.alloc((size_t)g.np * g.np));
+        TP_TRY(cd.y.alloc((size_t)g.np));
+        TP_TRY(cd.ctl.alloc_zero(1, s));
         cd.level = l;
     }
     cd.g = g;
@@ -212,17 +205,14 @@ int MGSolver<DOF>::coarse_direct_factor(int parts) {
     TP_LAUNCH((k_cd_fill<DOF>), dim3((g.np + CD_T - 1) / CD_T), dim3(CD_T), 0, s, o, g, cd.Lb);
     const int stages = sw_cd_stages();  // (timing aid: 1 fill, 2 + factor, 3 all)
     const bool prof_on = sw_cd_prof();  // (timing aid: ticks per phase, printed per factorisation)
-    long long *prof = nullptr;
-    if (prof_on) {
-        TP_HIP(hipMalloc((void **)&prof, sizeof(long long) * 8 * 32));
-        TP_HIP(hipMemsetAsync(prof, 0, sizeof(long long) * 8 * 32, s));
-    }
+    DevBuf<long long> prof;
+    if (prof_on) TP_TRY(prof.alloc_zero(8 * 32, s));
     if (stages >= 2) TP_LAUNCH(k_cd_factor, dim3(8 * P), dim3(CD_T), 0, s, g, cd.Lb, cd.Ld, cd.ctl, P, prof);
     if (prof_on) {
         long long h[8 * 32];
         TP_HIP(hipStreamSynchronize(s));
         TP_HIP(hipMemcpy(h, prof, sizeof(h), hipMemcpyDeviceToHost));
-        (void)hipFree(prof);
+        prof.reset();
         int rate = 100000;
         (void)hipDeviceGetAttribute(&rate, hipDeviceAttributeWallClockRate, 0);
         for (int r = 0; r < P; r += (P > 4 ? P / 3 : 1))
@@ -296,7 +286,7 @@ bool MGSolver<DOF>::xcd_gaveup() {
 
 template <int DOF>
 void MGSolver<DOF>::xcd_reset_controls() {
-    for (XcdRunCtrl *b : {run_ctl, lan_ctl, cd.ctl})
+    for (XcdRunCtrl *b : {run_ctl.p, lan_ctl.p, cd.ctl.p})
         if (b) (void)hipMemsetAsync(b, 0, sizeof(XcdRunCtrl), grid->stream);
     cd_early = cd_inverse_owed = false;
     cd.factored = false;
@@ -368,8 +358,7 @@ template <int DOF>
 int MGSolver<DOF>::coarse_run(int l, const double *b, int it0, int k, double sigma, double delta, int mode) {
     Level<DOF> &L = lv[l];
     if (!run_cnt) {
-        TP_HIP(hipMalloc((void **)&run_cnt, 2 * sizeof(unsigned long long)));
-        TP_HIP(hipMemset(run_cnt, 0, 2 * sizeof(unsigned long long)));
+        TP_TRY(run_cnt.alloc_zero(2));
     }
     ChebRunCoef cr;
     cr.nsteps = k - it0;
@@ -385,8 +374,7 @@ int MGSolver<DOF>::coarse_run(int l, const double *b, int it0, int k, double sig
         TP_LAUNCH((k_dia_cheb_run<DOF, 8, true>), dim3(1), dim3(RUN_WG), 0, grid->stream, o, b, L.dinv, L.d, L.x, L.x2, cr, run_cnt, run_base);
     } else if (mode == 3) {
         if (!run_ctl) {
-            TP_HIP(hipMalloc((void **)&run_ctl, sizeof(XcdRunCtrl)));
-            TP_HIP(hipMemsetAsync(run_ctl, 0, sizeof(XcdRunCtrl), grid->stream));
+            TP_TRY(run_ctl.alloc_zero(1, grid->stream));
         }
         int P;
         const int R = xcd_rows_per_thread(L.own_n(), &P);

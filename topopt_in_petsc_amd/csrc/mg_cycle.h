@@ -8,16 +8,9 @@ int MGSolver<DOF>::alloc_levels() {
     for (int l = 0; l < nlv; l++) {
         Level<DOF> &L = lv[l];
         L.g = make_geom(grid, l);
-        size_t nb = sizeof(double) * (size_t)L.ndof();
-        for (double **p : {&L.b, &L.x, &L.x2, &L.r, &L.d, &L.dinv}) {
-            TP_HIP(hipMalloc((void **)p, nb));
-            TP_HIP(hipMemsetAsync(*p, 0, nb, grid->stream));
-        }
+        TP_TRY(alloc_vectors(l));
     }
-    for (int i = nlv; i < LV_SLOTS; i++) {
-        lv[i] = Level<DOF>();
-        lv[i].b = lv[i].x = lv[i].x2 = lv[i].r = lv[i].d = lv[i].dinv = lv[i].S = lv[i].Kel = nullptr;
-    }
+    for (int i = nlv; i < LV_SLOTS; i++) lv[i] = Level<DOF>();  // (value-initialised: every pointer null)
     const bool no_rep = sw_no_replicate();
     replicate = allow_replicate && grid->has_comm && nlv > 1 && !no_rep;
     rep0 = nlv - 1;
@@ -60,20 +53,33 @@ int MGSolver<DOF>::alloc_levels() {
             R.g.has_lo = R.g.has_hi = 0;
             R.kind = LV_DIA;
             R.no_comm = true;
-            size_t rb = sizeof(double) * (size_t)R.ndof();
-            for (double **p : {&R.b, &R.x, &R.x2, &R.r, &R.d, &R.dinv}) {
-                TP_HIP(hipMalloc((void **)p, rb));
-                TP_HIP(hipMemsetAsync(*p, 0, rb, grid->stream));
-            }
-            TP_HIP(hipMalloc((void **)&R.S, rb * 28 * DOF));   // (+ DOF slices: row-sum correction of the mirrored reads)
-            TP_HIP(hipMemsetAsync(R.S, 0, rb * 28 * DOF, grid->stream));
+            TP_TRY(alloc_vectors(rix(l)));
+            TP_TRY(alloc_stencil(rix(l), 28 * DOF, true));   // (+ DOF slices: row-sum correction of the mirrored reads)
         }
     }
-    size_t nb = sizeof(double) * (size_t)lv[0].ndof();
-    for (double **p : {&cg_r, &cg_p, &cg_w, &cg_p2}) {
-        TP_HIP(hipMalloc((void **)p, nb));
-        TP_HIP(hipMemsetAsync(*p, 0, nb, grid->stream));
-    }
+    for (DevBuf<double> *p : {&cg_r, &cg_p, &cg_w, &cg_p2}) TP_TRY(p->alloc_zero((size_t)lv[0].ndof(), grid->stream));
+    return TP_OK;
+}
+
+template <int DOF>
+int MGSolver<DOF>::alloc_vectors(int i) {
+    Level<DOF> &L = lv[i];
+    LevelStore &st = store[i];
+    for (DevBuf<double> *p : {&st.b, &st.x, &st.x2, &st.r, &st.d, &st.dinv}) TP_TRY(p->alloc_zero((size_t)L.ndof(), grid->stream));
+    L.b = st.b, L.x = st.x, L.x2 = st.x2, L.r = st.r, L.d = st.d, L.dinv = st.dinv;
+    return TP_OK;
+}
+template <int DOF>
+int MGSolver<DOF>::alloc_stencil(int i, int slices, bool on_stream) {
+    const size_t n = (size_t)slices * (size_t)lv[i].ndof();
+    TP_TRY(on_stream ? store[i].S.alloc_zero(n, grid->stream) : store[i].S.alloc_zero(n));
+    lv[i].S = store[i].S;
+    return TP_OK;
+}
+template <int DOF>
+int MGSolver<DOF>::alloc_elem_matrices(int i) {
+    TP_TRY(store[i].Kel.alloc(576 * (size_t)lv[i].g.elems_stored()));
+    lv[i].Kel = store[i].Kel;
     return TP_OK;
 }
 
@@ -81,27 +87,10 @@ template <int DOF>
 void MGSolver<DOF>::free_levels() {
     smooth_graphs_free();
     refksp_free(*this);
-    for (int l = 0; l < LV_SLOTS; l++) {
-        Level<DOF> &L = lv[l];
-        if (l >= nlv && !(replicate && l < nlv + (nlv - rep0))) continue;   // unused slots
-        for (double *p : {L.b, L.x, L.x2, L.r, L.d, L.dinv, L.S, L.Kel}) (void)hipFree(p);
-    }
-    for (double *p : {cg_r, cg_p, cg_w, cg_p2}) (void)hipFree(p);
-    (void)hipFree(run_cnt);
-    run_cnt = nullptr;
-    (void)hipFree(run_ctl);
-    run_ctl = nullptr;
-    (void)hipFree(lan_ctl);
-    lan_ctl = nullptr;
     coarse_direct_free();
     for (LanBuf &b : lan) {
-        (void)hipFree(b.V);
-        (void)hipFree(b.coef);
-        (void)hipFree(b.part);
-        (void)hipFree(b.ticket);
-        (void)hipFree(b.mticket);
         (void)hipHostFree(b.hc);
-        b = LanBuf();
+        b.hc = nullptr;
     }
     for (int i = 0; i < LV_SLOTS; i++) {
         if (lan_graph[i]) (void)hipGraphExecDestroy(lan_graph[i]);

@@ -204,16 +204,13 @@ int MGSolver<DOF>::lanczos_enqueue(int l, int steps) {
     hipStream_t s = grid->stream;
     const size_t need = (size_t)nd * (size_t)(steps + 1);
     if (need > B.cap) {
-        (void)hipFree(B.V);
-        B.V = nullptr;
         B.cap = 0;
-        TP_HIP(hipMalloc((void **)&B.V, sizeof(double) * need));
-        B.cap = need;
         // zeroed once: the chain reads and writes the owned range of every basis vector only
-        TP_HIP(hipMemsetAsync(B.V, 0, sizeof(double) * need, s));
+        TP_TRY(B.V.alloc_zero(need, s));
+        B.cap = need;
     }
-    if (!B.coef) TP_HIP(hipMalloc((void **)&B.coef, sizeof(double) * 520));
-    if (!B.part) TP_HIP(hipMalloc((void **)&B.part, sizeof(double) * 256 * 130));
+    if (!B.coef) TP_TRY(B.coef.alloc(520));
+    if (!B.part) TP_TRY(B.part.alloc(256 * 130));
     if (!B.hc) TP_HIP(hipHostMalloc((void **)&B.hc, sizeof(double) * 520));
     // Round 6: the reductions of the chain end inside the kernels that produce them (TP_LANCZOS_TAILS=0: second launches, as
     // before) -- per step 3 launches of k_reduce_multi less, |w|^2 from the second Gram-Schmidt subtraction instead of a dot
@@ -221,10 +218,8 @@ int MGSolver<DOF>::lanczos_enqueue(int l, int steps) {
     // on level 1, 10 -> 6 on the stencil levels, 7 -> 6 where one workgroup per vector does the dot products.
     const bool tails = sw_lanczos_tails();
     if (tails && !B.ticket) {
-        TP_HIP(hipMalloc((void **)&B.ticket, sizeof(unsigned) * TICKET_WORDS));
-        TP_HIP(hipMalloc((void **)&B.mticket, sizeof(unsigned) * (size_t)MT_WORDS * 130));
-        TP_HIP(hipMemsetAsync(B.ticket, 0, sizeof(unsigned) * TICKET_WORDS, s));
-        TP_HIP(hipMemsetAsync(B.mticket, 0, sizeof(unsigned) * (size_t)MT_WORDS * 130, s));
+        TP_TRY(B.ticket.alloc_zero(TICKET_WORDS, s));
+        TP_TRY(B.mticket.alloc_zero((size_t)MT_WORDS * 130, s));
     }
     double *V = B.V, *coef = B.coef, *part = B.part;
     unsigned *mt = tails ? B.mticket : nullptr, *tk = tails ? B.ticket : nullptr;
@@ -292,12 +287,11 @@ int MGSolver<DOF>::lanczos_xcd(int l, int steps) {
     Level<DOF> &L = lv[l];
     LanBuf &B = lan[l];
     hipStream_t s = grid->stream;
-    if (!B.coef) TP_HIP(hipMalloc((void **)&B.coef, sizeof(double) * 520));
-    if (!B.part) TP_HIP(hipMalloc((void **)&B.part, sizeof(double) * 256 * 130));
+    if (!B.coef) TP_TRY(B.coef.alloc(520));
+    if (!B.part) TP_TRY(B.part.alloc(256 * 130));
     if (!B.hc) TP_HIP(hipHostMalloc((void **)&B.hc, sizeof(double) * 520));
     if (!lan_ctl) {
-        TP_HIP(hipMalloc((void **)&lan_ctl, sizeof(XcdRunCtrl)));
-        TP_HIP(hipMemsetAsync(lan_ctl, 0, sizeof(XcdRunCtrl), s));
+        TP_TRY(lan_ctl.alloc_zero(1, s));
     }
     TP_HIP(hipMemsetAsync(B.coef, 0, sizeof(double) * 520, s));
     DiaOp<DOF> o{L.S, L.ndof(), L.g};

@@ -210,11 +210,11 @@ struct tp_mma {
     double a[MMA_MAXM], c[MMA_MAXM], d[MMA_MAXM], y[MMA_MAXM], lam[MMA_MAXM], mu[MMA_MAXM], b[MMA_MAXM];
     double z;
     int robust, conmod;  // SetRobustAsymptotesType (0 | 1), ConstraintModification
-    double *L, *U, *alpha, *beta, *p0, *q0, *pij, *qij, *xo1, *xo2;
-    const double **d_dgdx;  // [dev] m pointers
-    double *red;            // [dev] m + m*m reduced values
-    double *part;           // [dev] (m + m*m) x 1024 block partials of the MMA kernels (own buffer: g->partials is
-                            //       sized for 4 values per block)
+    DevBuf<double> L, U, alpha, beta, p0, q0, pij, qij, xo1, xo2;
+    DevBuf<const double *> d_dgdx;  // [dev] m pointers
+    DevBuf<double> red;             // [dev] m + m*m reduced values
+    DevBuf<double> part;            // [dev] (m + m*m) x 1024 block partials of the MMA kernels (own buffer: g->partials is
+                                    //       sized for 4 values per block)
     int last_inner;
 };
 
@@ -237,7 +237,7 @@ static int mma_reduce(tp_mma *M, int nb, int nv, double *host) {
 
 extern "C" int tp_mma_create(tp_mma **out, tp_grid *g, long n_local, long n_global, int m, const double *x) {
     if (!out || !g || m < 1 || m > MMA_MAXM || m + m * m > 64) return TP_ERR_ARG;
-    tp_mma *M = new tp_mma();
+    std::unique_ptr<tp_mma> M(new tp_mma());
     M->grid = g;
     M->n = n_local;
     M->nglob = n_global;
@@ -255,27 +255,22 @@ extern "C" int tp_mma_create(tp_mma **out, tp_grid *g, long n_local, long n_glob
         M->y[j] = M->lam[j] = M->mu[j] = M->b[j] = 0.0;
     }
     const size_t nb = sizeof(double) * (size_t)n_local;
-    for (double **p : {&M->L, &M->U, &M->alpha, &M->beta, &M->p0, &M->q0, &M->xo1, &M->xo2}) {
-        TP_HIP(hipMalloc((void **)p, nb));
-        TP_HIP(hipMemsetAsync(*p, 0, nb, g->stream));
-    }
-    TP_HIP(hipMalloc((void **)&M->pij, nb * m));
-    TP_HIP(hipMalloc((void **)&M->qij, nb * m));
-    TP_HIP(hipMalloc((void **)&M->d_dgdx, sizeof(double *) * m));
-    TP_HIP(hipMalloc((void **)&M->red, sizeof(double) * 128));
-    TP_HIP(hipMalloc((void **)&M->part, sizeof(double) * 1024 * (size_t)(m + m * m)));
+    for (DevBuf<double> *p : {&M->L, &M->U, &M->alpha, &M->beta, &M->p0, &M->q0, &M->xo1, &M->xo2})
+        TP_TRY(p->alloc_zero((size_t)n_local, g->stream));
+    TP_TRY(M->pij.alloc((size_t)n_local * m));
+    TP_TRY(M->qij.alloc((size_t)n_local * m));
+    TP_TRY(M->d_dgdx.alloc(m));
+    TP_TRY(M->red.alloc(128));
+    TP_TRY(M->part.alloc(1024 * (size_t)(m + m * m)));
     TP_HIP(hipMemcpyAsync(M->xo1, x, nb, hipMemcpyDeviceToDevice, g->stream));
     TP_HIP(hipMemcpyAsync(M->xo2, x, nb, hipMemcpyDeviceToDevice, g->stream));
     M->last_inner = 0;
-    *out = M;
+    *out = M.release();
     return TP_OK;
 }
 extern "C" int tp_mma_destroy(tp_mma *M) {
     if (!M) return TP_OK;
     (void)hipStreamSynchronize(M->grid->stream);
-    for (void *p : {(void *)M->L, (void *)M->U, (void *)M->alpha, (void *)M->beta, (void *)M->p0, (void *)M->q0,
-                    (void *)M->xo1, (void *)M->xo2, (void *)M->pij, (void *)M->qij, (void *)M->d_dgdx, (void *)M->red, (void *)M->part})
-        (void)hipFree(p);
     delete M;
     return TP_OK;
 }

@@ -192,10 +192,10 @@ struct tp_overhang {
     double P, eps, xi0, Q;
     OvGeom q;
     long nel, pl;
-    double *ca, *cw, *cp;   // [dev, own elements] coefficients of the last forward sweep
-    double *xig, *pg;       // [dev, one layer] ghost layer of xi and its p (slabs)
-    double *medge[2];       // [dev, OV_MAXVEC layers] (w lambda) of the layer a transpose launch ended on, ping-pong
-    double *scratch;        // [dev, scratch_nv * own elements] out-of-place target of the transpose at C > 1, made on first use
+    DevBuf<double> ca, cw, cp;   // [dev, own elements] coefficients of the last forward sweep
+    DevBuf<double> xig, pg;      // [dev, one layer] ghost layer of xi and its p (slabs)
+    DevBuf<double> medge[2];     // [dev, OV_MAXVEC layers] (w lambda) of the layer a transpose launch ended on, ping-pong
+    DevBuf<double> scratch;      // [dev, scratch_nv * own elements] out-of-place target of the transpose at C > 1, made on first use
     int scratch_nv;
 };
 
@@ -219,7 +219,6 @@ static int overhang_pos(const tp_overhang *ov) { return ov->sign > 0 ? ov->grid-
 extern "C" int tp_overhang_destroy(tp_overhang *ov) {
     if (!ov) return TP_OK;
     (void)hipStreamSynchronize(ov->grid->stream);
-    for (double *p : {ov->ca, ov->cw, ov->cp, ov->xig, ov->pg, ov->medge[0], ov->medge[1], ov->scratch}) (void)hipFree(p);
     delete ov;
     return TP_OK;
 }
@@ -235,11 +234,11 @@ extern "C" int tp_overhang_set_params(tp_overhang *ov, double P, double eps, dou
 extern "C" int tp_overhang_create(tp_overhang **out, tp_grid *g, int axis, int sign) {
     if (!out || !g || (axis != 1 && axis != 2) || (sign != 1 && sign != -1)) return TP_ERR_ARG;
     if (g->nranks > 1 && axis != 2) return TP_ERR_ARG;  // the in-plane neighbours of a y build cross the slab border in every layer
-    tp_overhang *ov = new tp_overhang();
+    std::unique_ptr<tp_overhang> ov(new tp_overhang());
     ov->grid = g;
     ov->axis = axis;
     ov->sign = sign;
-    (void)tp_overhang_set_params(ov, 40.0, 1e-4, 0.5);
+    (void)tp_overhang_set_params(ov.get(), 40.0, 1e-4, 0.5);
     const long lay = (long)g->ex * g->ey;
     OvGeom &q = ov->q;
     q.ni = g->ex;
@@ -251,18 +250,10 @@ extern "C" int tp_overhang_create(tp_overhang **out, tp_grid *g, int axis, int s
     q.base = sign > 0 ? 0 : (q.nl - 1) * sl;
     ov->nel = lay * g->ez_own;
     ov->pl = (long)q.ni * q.nr;
-    auto body = [&]() -> int {
-        for (double **p : {&ov->ca, &ov->cw, &ov->cp}) TP_HIP(hipMalloc((void **)p, sizeof(double) * (size_t)ov->nel));
-        for (double **p : {&ov->xig, &ov->pg}) TP_HIP(hipMalloc((void **)p, sizeof(double) * (size_t)ov->pl));
-        for (double **p : {&ov->medge[0], &ov->medge[1]}) TP_HIP(hipMalloc((void **)p, sizeof(double) * (size_t)ov->pl * OV_MAXVEC));
-        return TP_OK;
-    };
-    const int rc = body();
-    if (rc) {
-        tp_overhang_destroy(ov);
-        return rc;
-    }
-    *out = ov;
+    for (DevBuf<double> *p : {&ov->ca, &ov->cw, &ov->cp}) TP_TRY(p->alloc((size_t)ov->nel));
+    for (DevBuf<double> *p : {&ov->xig, &ov->pg}) TP_TRY(p->alloc((size_t)ov->pl));
+    for (DevBuf<double> *p : {&ov->medge[0], &ov->medge[1]}) TP_TRY(p->alloc((size_t)ov->pl * OV_MAXVEC));
+    *out = ov.release();
     return TP_OK;
 }
 extern "C" int tp_overhang_last_chunk(const tp_overhang *ov) { return ov ? ov->last_chunk : 0; }
@@ -360,10 +351,8 @@ extern "C" int tp_overhang_adjoint(tp_overhang *ov, int nvec, double *const *gv)
     const int C = sw_overhang_chunk(), N = g->nranks, apos = N - 1 - overhang_pos(ov), G = overhang_group(C);
     if (C > 1 && ov->scratch_nv < (nvec < G ? nvec : G)) {
         TP_HIP(hipStreamSynchronize(g->stream));
-        (void)hipFree(ov->scratch);
-        ov->scratch = nullptr;
         ov->scratch_nv = 0;
-        TP_HIP(hipMalloc((void **)&ov->scratch, sizeof(double) * (size_t)(nvec < G ? nvec : G) * ov->nel));
+        TP_TRY(ov->scratch.alloc((size_t)(nvec < G ? nvec : G) * ov->nel));
         ov->scratch_nv = nvec < G ? nvec : G;
     }
     const int nchunks = (ov->q.nl + C - 1) / C;

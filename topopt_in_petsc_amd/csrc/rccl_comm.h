@@ -41,7 +41,7 @@ struct RcclComm {
     hipStream_t home_stream = nullptr;  // the grid's stream
     int rank = 0, nranks = 1;
     bool periodic = false;  // self test only: the single rank is its own lower and upper neighbour
-    double *buf = nullptr;  // owns send_lo | send_hi | recv_lo | recv_hi | red | gather
+    DevBuf<double> buf;     // owns send_lo | send_hi | recv_lo | recv_hi | red | gather
     tp_comm hooks{};
     long n_exchanges = 0, n_reductions = 0;
 };
@@ -158,7 +158,7 @@ inline int rccl_comm_create(RcclComm **out, const void *id128, int rank, int nra
         }
     }
     const size_t total = (size_t)cap * (4 + (size_t)nranks) + 16;
-    if (hipMalloc((void **)&c->buf, sizeof(double) * total) != hipSuccess) {
+    if (c->buf.alloc(total)) {
         if (c->comm_halo) A.CommDestroy(c->comm_halo);
         A.CommDestroy(c->comm);
         delete c;
@@ -188,6 +188,5 @@ inline void rccl_comm_destroy(RcclComm *c) {
     (void)hipStreamSynchronize(c->home_stream);
     if (c->comm_halo) rccl_api().CommDestroy(c->comm_halo);
     if (c->comm) rccl_api().CommDestroy(c->comm);
-    (void)hipFree(c->buf);
     delete c;
 }

@@ -65,54 +65,34 @@ struct RefKsp {
     static constexpr int CH = 8;  // basis vectors per allocation (FGMRES(100) grows as PETSc's does, not up front)
     static constexpr int NCOEF = 256, SLOT_NORM = 250;
     struct Basis {
-        std::vector<double *> chunk;
+        std::vector<DevBuf<double>> chunk;
         long nd = 0;
         double *vec(int j) const { return chunk[j / CH] + (long)(j % CH) * nd; }
     };
     Basis lvV[TP_MAX_LEVELS + 1];         // Krylov bases of the level solvers
-    double *lvT[TP_MAX_LEVELS + 1] = {};  // level scratch: operator output / residual
+    DevBuf<double> lvT[TP_MAX_LEVELS + 1];  // level scratch: operator output / residual
     Basis oV, oZ;                         // outer FGMRES: Krylov basis and the preconditioned directions
-    double *coef = nullptr, *part = nullptr, *hc = nullptr;  // device coefficients, reduction partials, pinned host copy
+    DevBuf<double> coef, part;            // device coefficients, reduction partials
+    double *hc = nullptr;                 // pinned host copy of the coefficients
     long sweeps = 0;                      // Gauss-Seidel sweeps of the last solve (diagnostics)
 
     int ensure(Basis &B, int last, long nd) {
         B.nd = nd;
         while ((int)B.chunk.size() * CH <= last) {
-            double *p = nullptr;
-            TP_HIP(hipMalloc((void **)&p, sizeof(double) * (size_t)nd * CH));
-            TP_HIP(hipMemsetAsync(p, 0, sizeof(double) * (size_t)nd * CH, grid->stream));
-            B.chunk.push_back(p);
+            DevBuf<double> p;
+            TP_TRY(p.alloc_zero((size_t)nd * CH, grid->stream));
+            B.chunk.push_back(std::move(p));
         }
         return TP_OK;
-    }
-    static void release(Basis &B) {
-        for (double *p : B.chunk) (void)hipFree(p);
-        B.chunk.clear();
     }
     int init() {
-        TP_HIP(hipMalloc((void **)&coef, sizeof(double) * NCOEF));
-        TP_HIP(hipMalloc((void **)&part, sizeof(double) * 256 * CH));
+        TP_TRY(coef.alloc(NCOEF));
+        TP_TRY(part.alloc(256 * CH));
         TP_HIP(hipHostMalloc((void **)&hc, sizeof(double) * NCOEF));
-        for (int l = 0; l < mg->nlv; l++) {
-            const size_t nb = sizeof(double) * (size_t)mg->lv[l].ndof();
-            TP_HIP(hipMalloc((void **)&lvT[l], nb));
-            TP_HIP(hipMemsetAsync(lvT[l], 0, nb, grid->stream));
-        }
+        for (int l = 0; l < mg->nlv; l++) TP_TRY(lvT[l].alloc_zero((size_t)mg->lv[l].ndof(), grid->stream));
         return TP_OK;
     }
-    void free_all() {
-        for (int l = 0; l <= TP_MAX_LEVELS; l++) {
-            release(lvV[l]);
-            (void)hipFree(lvT[l]);
-            lvT[l] = nullptr;
-        }
-        release(oV);
-        release(oZ);
-        (void)hipFree(coef);
-        (void)hipFree(part);
-        (void)hipHostFree(hc);
-        coef = part = hc = nullptr;
-    }
+    ~RefKsp() { (void)hipHostFree(hc); }
 
     // ---- BLAS-1 on the owned range of level l -------------------------------------------------
     int read_coef(int first, int n, double *out) {
@@ -451,11 +431,7 @@ int refksp_solve(MGSolver<DOF> &mg, const double *b, double *x, int *its, double
 }
 template <int DOF>
 void refksp_free(MGSolver<DOF> &mg) {
-    RefKsp<DOF> *R = static_cast<RefKsp<DOF> *>(mg.refksp);
-    if (R) {
-        R->free_all();
-        delete R;
-    }
+    delete static_cast<RefKsp<DOF> *>(mg.refksp);
     mg.refksp = nullptr;
 }
 template <int DOF>

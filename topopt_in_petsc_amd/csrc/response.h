@@ -182,10 +182,8 @@ extern "C" int tp_elasticity_response(tp_elasticity *e, int ncase, const double 
     } else {
         if (e->resp_nb < nb) {  // (the grid's own partials hold four values per workgroup)
             TP_HIP(hipStreamSynchronize(g->stream));
-            (void)hipFree(e->d_resp);
-            e->d_resp = nullptr;
             e->resp_nb = 0;
-            TP_HIP(hipMalloc((void **)&e->d_resp, sizeof(double) * (TP_MAX_CASES + 1) * (size_t)nb));
+            TP_TRY(e->d_resp.alloc((TP_MAX_CASES + 1) * (size_t)nb));
             e->resp_nb = nb;
         }
         TP_TRY(launch(true, e->d_resp));

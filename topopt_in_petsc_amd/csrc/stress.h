@@ -124,10 +124,7 @@ extern "C" int tp_elasticity_stress(tp_elasticity *e, const double *U, const dou
     }
     double *sc = nullptr;
     if (dpdx || adj_rhs) {
-        if (!e->d_sx) {
-            TP_HIP(hipMalloc((void **)&e->d_sx, sizeof(double) * (size_t)(nel + lay)));
-            TP_HIP(hipMemsetAsync(e->d_sx, 0, sizeof(double) * (size_t)(nel + lay), g->stream));
-        }
+        if (!e->d_sx) TP_TRY(e->d_sx.alloc_zero((size_t)(nel + lay), g->stream));
         sc = e->d_sx;
     }
     TP_LAUNCH(k_stress_elem<true>, dim3(nb), dim3(BLK), 0, g->stream, geo, e->d_VM, U, xPhys, Emax, q, P, vm, sc, g->partials);

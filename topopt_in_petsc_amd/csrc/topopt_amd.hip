@@ -1,5 +1,6 @@
 // topopt_amd.hip -- C-ABI entry points (include/topopt_amd.h) of the MI355X-native
 // hot path.  gfx950 only; no CPU fallback anywhere in this library.
+#include <memory>
 #include <string>
 
 #include "elements.h"
@@ -16,7 +17,7 @@ extern "C" int tp_grid_create(tp_grid **out, const tp_grid_opts *o) {
     if ((o->nz - 1) % o->nranks) return TP_ERR_ARG;
     if (o->nranks > 1 && !o->comm) return TP_ERR_ARG;
     TP_HIP(hipSetDevice(o->device));
-    tp_grid *g = new tp_grid();
+    std::unique_ptr<tp_grid> g(new tp_grid());
     g->o = *o;
     g->stream = (hipStream_t)o->stream;
     g->has_comm = o->nranks > 1;
@@ -38,16 +39,12 @@ extern "C" int tp_grid_create(tp_grid **out, const tp_grid_opts *o) {
     g->nranks = o->nranks;
     g->alg_bytes = g->flops = 0.0;
     g->launches = 0;
-    Geom q = make_geom(g, 0);
+    Geom q = make_geom(g.get(), 0);
     long nblk = q.nodes() / BLK + 2;
     if (nblk < MAX_RED_BLOCKS) nblk = MAX_RED_BLOCKS;
-    if (hipMalloc((void **)&g->partials, sizeof(double) * 4 * (size_t)nblk) != hipSuccess ||
-        hipMalloc((void **)&g->scal, sizeof(double) * 64) != hipSuccess ||
-        hipMalloc((void **)&g->ticket, sizeof(unsigned) * TICKET_WORDS) != hipSuccess ||
-        hipHostMalloc((void **)&g->h_scal, sizeof(double) * 64) != hipSuccess) {
-        delete g;
+    if (g->partials.alloc(4 * (size_t)nblk) || g->scal.alloc(64) || g->ticket.alloc(TICKET_WORDS) ||
+        hipHostMalloc((void **)&g->h_scal, sizeof(double) * 64) != hipSuccess)
         return TP_ERR_HIP + (int)hipErrorOutOfMemory;
-    }
     g->h_scal_dev = nullptr;
     if (hipHostGetDevicePointer((void **)&g->h_scal_dev, g->h_scal, 0) != hipSuccess) {
         (void)hipGetLastError();
@@ -58,7 +55,7 @@ extern "C" int tp_grid_create(tp_grid **out, const tp_grid_opts *o) {
     double W[512];
     host_W(W);
     TP_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_W), W, sizeof(W)));
-    *out = g;
+    *out = g.release();
     return TP_OK;
 }
 extern "C" int tp_rccl_load(const char *path) { return rccl_load(path); }
@@ -99,20 +96,11 @@ __global__ __launch_bounds__(BLK) void k_selftest_fill(double *a, double *b, lon
 }
 extern "C" int tp_grid_reduction_selftest(tp_grid *g, long n, int reps, int *mismatches) {
     if (!g || n < 1 || reps < 1 || reps > 4096 || !mismatches) return TP_ERR_ARG;
-    double *a = nullptr, *b = nullptr, *res = nullptr;
-    struct Guard {  // the early returns of TP_HIP / TP_LAUNCH free the buffers too
-        double *&a, *&b, *&r;
-        hipStream_t s;
-        ~Guard() {
-            (void)hipStreamSynchronize(s);
-            (void)hipFree(a);
-            (void)hipFree(b);
-            (void)hipFree(r);
-        }
-    } guard{a, b, res, g->stream};
-    TP_HIP(hipMalloc((void **)&a, sizeof(double) * (size_t)n));
-    TP_HIP(hipMalloc((void **)&b, sizeof(double) * (size_t)n));
-    TP_HIP(hipMalloc((void **)&res, sizeof(double) * 2 * (size_t)reps));
+    DevBuf<double> a, b, res;
+    StreamSyncAtExit sync{g->stream};  // (declared last: the early returns of TP_HIP / TP_LAUNCH wait before the buffers die)
+    TP_TRY(a.alloc((size_t)n));
+    TP_TRY(b.alloc((size_t)n));
+    TP_TRY(res.alloc(2 * (size_t)reps));
     const int nb = grid_for(n, 2048);
     for (int r = 0; r < reps; r++) {
         if (r % 16 == 0) TP_LAUNCH(k_selftest_fill, dim3(grid_for(n)), dim3(BLK), 0, g->stream, a, b, n, (uint64_t)(1000 + r));
@@ -370,21 +358,20 @@ extern "C" int tp_rccl_selftest(int device, void *stream, long n, double *max_er
     *max_err = err;
     return rc ? TP_ERR_COMM : TP_OK;
 }
+tp_grid::~tp_grid() {
+    rccl_comm_destroy(rccl);
+    if (comm_stream) {
+        (void)hipStreamSynchronize(comm_stream);
+        (void)hipStreamDestroy(comm_stream);
+    }
+    if (ev_ready) (void)hipEventDestroy(ev_ready);
+    if (ev_scal) (void)hipEventDestroy(ev_scal);
+    for (hipEvent_t e : kt_ev) (void)hipEventDestroy(e);  // a kernel timer that was never read
+    (void)hipHostFree(h_scal);
+}
 extern "C" int tp_grid_destroy(tp_grid *g) {
     if (!g) return TP_OK;
     (void)hipStreamSynchronize(g->stream);
-    rccl_comm_destroy(g->rccl);
-    if (g->comm_stream) {
-        (void)hipStreamSynchronize(g->comm_stream);
-        (void)hipStreamDestroy(g->comm_stream);
-    }
-    if (g->ev_ready) (void)hipEventDestroy(g->ev_ready);
-    if (g->ev_scal) (void)hipEventDestroy(g->ev_scal);
-    for (hipEvent_t e : g->kt_ev) (void)hipEventDestroy(e);  // a kernel timer that was never read
-    (void)hipFree(g->partials);
-    (void)hipFree(g->scal);
-    (void)hipFree(g->ticket);
-    (void)hipHostFree(g->h_scal);
     delete g;
     return TP_OK;
 }
@@ -407,13 +394,14 @@ extern "C" int tp_set_device(int device) {
     return TP_OK;
 }
 extern "C" int tp_malloc(void **p, size_t bytes) {
-    TP_HIP(hipMalloc(p, bytes));
+    TP_HIP(dev_raw_malloc(p, bytes));
     return TP_OK;
 }
 extern "C" int tp_free(void *p) {
-    TP_HIP(hipFree(p));
+    TP_HIP(dev_raw_free(p));
     return TP_OK;
 }
+extern "C" long long tp_device_bytes_live(void) { return dev_bytes_live().load(); }
 extern "C" int tp_memcpy_h2d(void *dst, const void *src, size_t bytes) {
     TP_HIP(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
     return TP_OK;
@@ -511,35 +499,41 @@ struct tp_elasticity {
     hipStream_t aux_stream = nullptr;            // level 2's Galerkin kernel beside level 1's (assemble)
     hipEvent_t aux_fork = nullptr, aux_done = nullptr;
     double KE[576];
-    double *d_KE, *d_M;      // element matrix, 8 child matrices (level 0 -> 1 fast path)
-    double *d_E;             // SIMP moduli, own + ghost-above layer
-    uint8_t *d_mask;         // clamped-dof bits per local node
-    uint8_t *d_colmask;      // OR of d_mask over the planes of a node column
+    DevBuf<double> d_KE, d_M;    // element matrix, 8 child matrices (level 0 -> 1 fast path)
+    DevBuf<double> d_E;          // SIMP moduli, own + ghost-above layer
+    DevBuf<uint8_t> d_mask;      // clamped-dof bits per local node
+    DevBuf<uint8_t> d_colmask;   // OR of d_mask over the planes of a node column
     std::vector<uint8_t> h_mask;
-    int *d_flagged;          // level-1 elements touching clamped nodes
-    int *d_flag_all;         // flagged level-1 elements incl. the ghost layer (matrix-free level 1)
-    int nflag_all;
-    int *d_corr_nodes, *d_corr_adj;
-    double *d_dK, *d_corr, *d_corr_tmp;
+    DevBuf<int> d_flagged;       // level-1 elements touching clamped nodes
+    DevBuf<int> d_flag_all;      // flagged level-1 elements incl. the ghost layer (matrix-free level 1)
+    int nflag_all = 0;
+    DevBuf<int> d_corr_nodes, d_corr_adj;
+    DevBuf<double> d_dK, d_corr, d_corr_tmp;
     // matrix-free level 1 keeps no element matrices but those of the flagged elements (compact rows: own flagged in
     // list order, then the ghost-layer ones received from the upper neighbour) and the element -> row map
-    double *d_KelF;
-    int *d_fidx1;
-    double *d_M2;            // 64 grand-child matrices (level 0 -> 2 in one step)
-    uint8_t *d_flag2;        // own level-2 elements with a flagged level-1 child
-    int *d_list2;            // ... as a list
-    int nlist2;
-    int nx_first;            // max over ranks of the flagged elements in a rank's first own level-1 layer
-    int nflagged;
-    double *d_bN;            // RHS .* N scratch
-    double *d_N;             // copy of N (for the load masking of :542)
-    double VM[576];            // von Mises form of the element (elements.h: hex8_vonmises_form_box), always from the grid's h and opts.nu
-    double *d_VM = nullptr;    // ... on the device, beside d_KE
-    double *d_sx = nullptr;    // tp_elasticity_stress: per-element scratch between its passes, own + ghost-above layer (first use)
-    double *d_resp = nullptr;  // block partials of tp_elasticity_response, (TP_MAX_CASES + 1) x resp_nb, allocated by its first sums
+    DevBuf<double> d_KelF;
+    DevBuf<int> d_fidx1;
+    DevBuf<double> d_M2;         // 64 grand-child matrices (level 0 -> 2 in one step)
+    DevBuf<uint8_t> d_flag2;     // own level-2 elements with a flagged level-1 child
+    DevBuf<int> d_list2;         // ... as a list
+    int nlist2 = 0;
+    int nx_first = 0;        // max over ranks of the flagged elements in a rank's first own level-1 layer
+    int nflagged = 0;
+    DevBuf<double> d_bN;         // RHS .* N scratch
+    DevBuf<double> d_N;          // copy of N (for the load masking of :542)
+    double VM[576];          // von Mises form of the element (elements.h: hex8_vonmises_form_box), always from the grid's h and opts.nu
+    DevBuf<double> d_VM;         // ... on the device, beside d_KE
+    DevBuf<double> d_sx;         // tp_elasticity_stress: per-element scratch between its passes, own + ghost-above layer (first use)
+    DevBuf<double> d_resp;       // block partials of tp_elasticity_response, (TP_MAX_CASES + 1) x resp_nb, allocated by its first sums
     long resp_nb = 0;
-    double *d_xg = nullptr;    // tp_elasticity_body_load: the upper neighbour's first own layer of xPhys (slabs, first use)
-    bool have_bc, assembled;
+    DevBuf<double> d_xg;         // tp_elasticity_body_load: the upper neighbour's first own layer of xPhys (slabs, first use)
+    bool have_bc = false, assembled = false;
+    ~tp_elasticity() {
+        sym_slot_release(mg.lv[0].sym_slot);
+        if (aux_stream) (void)hipStreamDestroy(aux_stream);
+        if (aux_fork) (void)hipEventDestroy(aux_fork);
+        if (aux_done) (void)hipEventDestroy(aux_done);
+    }
 };
 
 __global__ __launch_bounds__(BLK) void k_simp(const double *__restrict__ x, double Emin, double Emax, double penal,
@@ -598,7 +592,7 @@ extern "C" int tp_elasticity_create_ke(tp_elasticity **out, tp_grid *g, const tp
             return TP_ERR_ARG;
         }
     }
-    tp_elasticity *e = new tp_elasticity();
+    std::unique_ptr<tp_elasticity> e(new tp_elasticity());
     e->grid = g;
     e->mg.grid = g;
     e->mg.nlv = o->nlvls;
@@ -606,20 +600,6 @@ extern "C" int tp_elasticity_create_ke(tp_elasticity **out, tp_grid *g, const tp
     // the replicated copy of the coarsest level is a stored stencil: levels >= 2 are; with two levels the coarsest one is
     // level 1, applied from the fine moduli (no stencil to gather) -- it stays distributed
     e->mg.allow_replicate = o->nlvls >= 3;
-    e->have_bc = e->assembled = false;
-    e->d_flagged = nullptr;
-    e->nflagged = 0;
-    e->d_colmask = nullptr;
-    e->d_flag_all = e->d_corr_nodes = e->d_corr_adj = nullptr;
-    e->d_dK = e->d_corr = e->d_corr_tmp = nullptr;
-    e->d_KelF = nullptr;
-    e->d_fidx1 = nullptr;
-    e->d_M2 = nullptr;
-    e->d_flag2 = nullptr;
-    e->d_list2 = nullptr;
-    e->nlist2 = 0;
-    e->nx_first = 0;
-    e->nflag_all = 0;
     if (ke_host_576) std::memcpy(e->KE, ke_host_576, sizeof(e->KE));
     else hex8_stiffness_box(g->o.hx, g->o.hy, g->o.hz, o->nu, e->KE);
     hex8_vonmises_form_box(g->o.hx, g->o.hy, g->o.hz, o->nu, e->VM);
@@ -627,21 +607,20 @@ extern "C" int tp_elasticity_create_ke(tp_elasticity **out, tp_grid *g, const tp
     host_child_matrices(e->KE, M.data());
     TP_TRY(e->mg.alloc_levels());
     Geom q = make_geom(g, 0);
-    TP_HIP(hipMalloc((void **)&e->d_KE, sizeof(double) * 576));
-    TP_HIP(hipMalloc((void **)&e->d_M, sizeof(double) * 8 * 576));
-    TP_HIP(hipMalloc((void **)&e->d_E, sizeof(double) * (size_t)((long)q.ex * q.ey * (q.ez_own + 2))));
-    TP_HIP(hipMemset(e->d_E, 0, sizeof(double) * (size_t)((long)q.ex * q.ey * (q.ez_own + 2))));
-    TP_HIP(hipMalloc((void **)&e->d_mask, (size_t)q.nodes()));
-    TP_HIP(hipMalloc((void **)&e->d_bN, sizeof(double) * 3 * (size_t)q.nodes()));
-    TP_HIP(hipMalloc((void **)&e->d_N, sizeof(double) * 3 * (size_t)q.nodes()));
+    TP_TRY(e->d_KE.alloc(576));
+    TP_TRY(e->d_M.alloc(8 * 576));
+    TP_TRY(e->d_E.alloc_zero((size_t)((long)q.ex * q.ey * (q.ez_own + 2))));
+    TP_TRY(e->d_mask.alloc((size_t)q.nodes()));
+    TP_TRY(e->d_bN.alloc(3 * (size_t)q.nodes()));
+    TP_TRY(e->d_N.alloc(3 * (size_t)q.nodes()));
     TP_HIP(hipMemcpy(e->d_KE, e->KE, sizeof(double) * 576, hipMemcpyHostToDevice));
-    TP_HIP(hipMalloc((void **)&e->d_VM, sizeof(double) * 576));
+    TP_TRY(e->d_VM.alloc(576));
     TP_HIP(hipMemcpy(e->d_VM, e->VM, sizeof(double) * 576, hipMemcpyHostToDevice));
     TP_HIP(hipMemcpy(e->d_M, M.data(), sizeof(double) * 8 * 576, hipMemcpyHostToDevice));
     {
         std::vector<double> M2((size_t)64 * 576);
         host_grandchild_matrices(M.data(), M2.data());
-        TP_HIP(hipMalloc((void **)&e->d_M2, sizeof(double) * M2.size()));
+        TP_TRY(e->d_M2.alloc(M2.size()));
         TP_HIP(hipMemcpy(e->d_M2, M2.data(), sizeof(double) * M2.size(), hipMemcpyHostToDevice));
     }
     TP_HIP(hipMemset(e->d_mask, 0, (size_t)q.nodes()));
@@ -651,14 +630,12 @@ extern "C" int tp_elasticity_create_ke(tp_elasticity **out, tp_grid *g, const tp
         L.KE = e->d_KE;
         L.E = e->d_E;
         L.mask = e->d_mask;
-        L.S = L.Kel = nullptr;
         if (l == 0) {
             // tuned kernel needs the reflection symmetry of a box element (always true here)
             SymKE sk;
             const double asym = make_sym_ke(e->KE, &sk);
             L.sym_slot = (asym < 1e-12 && !sw_no_tile()) ? sym_slot_acquire(sk) : -1;
-            TP_HIP(hipMalloc((void **)&e->d_colmask, (size_t)q.plane()));
-            TP_HIP(hipMemset(e->d_colmask, 0, (size_t)q.plane()));
+            TP_TRY(e->d_colmask.alloc_zero((size_t)q.plane()));
             L.colmask = e->d_colmask;
             L.use_tile = L.sym_slot >= 0;
         }
@@ -674,37 +651,22 @@ extern "C" int tp_elasticity_create_ke(tp_elasticity **out, tp_grid *g, const tp
             }
             L.fex = q.ex;
             L.fey = q.ey;
-            TP_HIP(hipMalloc((void **)&e->d_corr, sizeof(double) * (size_t)L.ndof()));
-            TP_HIP(hipMemset(e->d_corr, 0, sizeof(double) * (size_t)L.ndof()));
+            TP_TRY(e->d_corr.alloc_zero((size_t)L.ndof()));
             L.corr = e->d_corr;
         }
         if (l > 0) {
-            if (L.kind == LV_DIA) {
-                // 81 diagonals + 3 slices for the row-sum correction of the mirrored reads (operators.h: k_dia_sym_fix)
-                TP_HIP(hipMalloc((void **)&L.S, sizeof(double) * 84 * (size_t)L.ndof()));
-                TP_HIP(hipMemset(L.S, 0, sizeof(double) * 84 * (size_t)L.ndof()));
-            }
+            // 81 diagonals + 3 slices for the row-sum correction of the mirrored reads (operators.h: k_dia_sym_fix)
+            if (L.kind == LV_DIA) TP_TRY(e->mg.alloc_stencil(l, 84, false));
             // the matrix-free level 1 materialises no element matrices (1.2 GB at 128^3)
-            if (L.kind != LV_MACRO) TP_HIP(hipMalloc((void **)&L.Kel, sizeof(double) * 576 * (size_t)L.g.elems_stored()));
+            if (L.kind != LV_MACRO) TP_TRY(e->mg.alloc_elem_matrices(l));
         }
     }
-    *out = e;
+    *out = e.release();
     return TP_OK;
 }
 extern "C" int tp_elasticity_destroy(tp_elasticity *e) {
     if (!e) return TP_OK;
     (void)hipStreamSynchronize(e->grid->stream);
-    sym_slot_release(e->mg.lv[0].sym_slot);
-    e->mg.free_levels();
-    if (e->aux_stream) (void)hipStreamDestroy(e->aux_stream);
-    if (e->aux_fork) (void)hipEventDestroy(e->aux_fork);
-    if (e->aux_done) (void)hipEventDestroy(e->aux_done);
-    for (void *p : {(void *)e->d_KE, (void *)e->d_M, (void *)e->d_E, (void *)e->d_mask, (void *)e->d_bN, (void *)e->d_N,
-                    (void *)e->d_flagged, (void *)e->d_colmask, (void *)e->d_flag_all, (void *)e->d_corr_nodes,
-                    (void *)e->d_corr_adj, (void *)e->d_dK, (void *)e->d_corr, (void *)e->d_corr_tmp, (void *)e->d_KelF,
-                    (void *)e->d_fidx1, (void *)e->d_M2, (void *)e->d_flag2, (void *)e->d_list2, (void *)e->d_resp,
-                    (void *)e->d_VM, (void *)e->d_sx, (void *)e->d_xg})
-        (void)hipFree(p);
     delete e;
     return TP_OK;
 }
@@ -798,8 +760,7 @@ extern "C" int tp_elasticity_set_bc(tp_elasticity *e, const double *N) {
                     if (any) fl.push_back(I + c.ex * (J + c.ey * K));
                 }
     }
-    (void)hipFree(e->d_flagged);
-    e->d_flagged = nullptr;
+    e->d_flagged.reset();
     e->nflagged = (int)fl.size();
     if (e->mg.nlv > 1 && e->mg.lv[1].kind == LV_MACRO) {
         // matrix-free level 1: flagged elements incl. the ghost layer above (flags of the upper
@@ -810,13 +771,13 @@ extern "C" int tp_elasticity_set_bc(tp_elasticity *e, const double *N) {
         std::vector<double> fl_d((size_t)c.elems_stored(), 0.0);
         for (int id : fl) fl_d[(size_t)id] = 1.0;
         if (g->has_comm) {
-            double *tmp;
-            TP_HIP(hipMalloc((void **)&tmp, sizeof(double) * fl_d.size()));
+            DevBuf<double> tmp;
+            StreamSyncAtExit sync{g->stream};
+            TP_TRY(tmp.alloc(fl_d.size()));
             TP_HIP(hipMemcpy(tmp, fl_d.data(), sizeof(double) * fl_d.size(), hipMemcpyHostToDevice));
             TP_TRY(exchange_segments(g, tmp, nullptr, nullptr, tmp + clay * c.ez_own, clay, 1, clay));
             TP_HIP(hipStreamSynchronize(g->stream));
             TP_HIP(hipMemcpy(fl_d.data(), tmp, sizeof(double) * fl_d.size(), hipMemcpyDeviceToHost));
-            (void)hipFree(tmp);
         }
         std::vector<int> fall, fidx((size_t)c.elems_stored(), -1);
         for (size_t i = 0; i < fl_d.size(); i++)
@@ -842,12 +803,8 @@ extern "C" int tp_elasticity_set_bc(tp_elasticity *e, const double *N) {
                         cadj.insert(cadj.end(), adj, adj + 8);
                     }
                 }
-        for (void *p : {(void *)e->d_flag_all, (void *)e->d_corr_nodes, (void *)e->d_corr_adj, (void *)e->d_dK,
-                        (void *)e->d_corr_tmp, (void *)e->d_KelF, (void *)e->d_fidx1})
-            (void)hipFree(p);
-        e->d_flag_all = e->d_corr_nodes = e->d_corr_adj = nullptr;
-        e->d_dK = e->d_corr_tmp = e->d_KelF = nullptr;
-        e->d_fidx1 = nullptr;
+        for (DevBuf<int> *p : {&e->d_flag_all, &e->d_corr_nodes, &e->d_corr_adj, &e->d_fidx1}) p->reset();
+        for (DevBuf<double> *p : {&e->d_dK, &e->d_corr_tmp, &e->d_KelF}) p->reset();
         // own flagged elements come first in `fall` (same order as `fl`), the ghost layer last; the first own layer
         // is the head of `fl`.  The compact ghost rows travel down with a common row count (max over the ranks).
         int n0 = 0;
@@ -865,12 +822,10 @@ extern "C" int tp_elasticity_set_bc(tp_elasticity *e, const double *N) {
             }
             for (double v : cnt) e->nx_first = v > e->nx_first ? (int)v : e->nx_first;
         }
-        TP_HIP(hipMalloc((void **)&e->d_fidx1, sizeof(int) * fidx.size()));
+        TP_TRY(e->d_fidx1.alloc(fidx.size()));
         TP_HIP(hipMemcpy(e->d_fidx1, fidx.data(), sizeof(int) * fidx.size(), hipMemcpyHostToDevice));
-        (void)hipFree(e->d_flag2);
-        (void)hipFree(e->d_list2);
-        e->d_flag2 = nullptr;
-        e->d_list2 = nullptr;
+        e->d_flag2.reset();
+        e->d_list2.reset();
         e->nlist2 = 0;
         if (e->mg.nlv > 2) {  // own level-2 elements with a flagged child take the generic construction
             Geom c2 = make_geom(g, 2);
@@ -887,31 +842,30 @@ extern "C" int tp_elasticity_set_bc(tp_elasticity *e, const double *N) {
                             l2.push_back(I + c2.ex * (J + c2.ey * K));
                         }
                     }
-            TP_HIP(hipMalloc((void **)&e->d_flag2, f2.size() + 1));
+            TP_TRY(e->d_flag2.alloc(f2.size() + 1));
             TP_HIP(hipMemcpy(e->d_flag2, f2.data(), f2.size(), hipMemcpyHostToDevice));
             e->nlist2 = (int)l2.size();
             if (!l2.empty()) {
-                TP_HIP(hipMalloc((void **)&e->d_list2, sizeof(int) * l2.size()));
+                TP_TRY(e->d_list2.alloc(l2.size()));
                 TP_HIP(hipMemcpy(e->d_list2, l2.data(), sizeof(int) * l2.size(), hipMemcpyHostToDevice));
             }
         }
         {
             const size_t rows = fl.size() + 2 * (size_t)e->nx_first + 1;
-            TP_HIP(hipMalloc((void **)&e->d_KelF, sizeof(double) * 576 * rows));
-            TP_HIP(hipMemset(e->d_KelF, 0, sizeof(double) * 576 * rows));
+            TP_TRY(e->d_KelF.alloc_zero(576 * rows));
         }
         e->nflag_all = (int)fall.size();
         TP_HIP(hipMemset(e->d_corr, 0, sizeof(double) * (size_t)L1.ndof()));
         if (!fall.empty()) {
-            TP_HIP(hipMalloc((void **)&e->d_flag_all, sizeof(int) * fall.size()));
+            TP_TRY(e->d_flag_all.alloc(fall.size()));
             TP_HIP(hipMemcpy(e->d_flag_all, fall.data(), sizeof(int) * fall.size(), hipMemcpyHostToDevice));
-            TP_HIP(hipMalloc((void **)&e->d_dK, sizeof(double) * 576 * fall.size()));
-            TP_HIP(hipMalloc((void **)&e->d_corr_tmp, sizeof(double) * 24 * fall.size()));
+            TP_TRY(e->d_dK.alloc(576 * fall.size()));
+            TP_TRY(e->d_corr_tmp.alloc(24 * fall.size()));
         }
         if (!cn.empty()) {
-            TP_HIP(hipMalloc((void **)&e->d_corr_nodes, sizeof(int) * cn.size()));
+            TP_TRY(e->d_corr_nodes.alloc(cn.size()));
             TP_HIP(hipMemcpy(e->d_corr_nodes, cn.data(), sizeof(int) * cn.size(), hipMemcpyHostToDevice));
-            TP_HIP(hipMalloc((void **)&e->d_corr_adj, sizeof(int) * cadj.size()));
+            TP_TRY(e->d_corr_adj.alloc(cadj.size()));
             TP_HIP(hipMemcpy(e->d_corr_adj, cadj.data(), sizeof(int) * cadj.size(), hipMemcpyHostToDevice));
         }
         L1.dK = e->d_dK;
@@ -923,7 +877,7 @@ extern "C" int tp_elasticity_set_bc(tp_elasticity *e, const double *N) {
         L1.corr_tmp = e->d_corr_tmp;
     }
     if (e->nflagged) {
-        TP_HIP(hipMalloc((void **)&e->d_flagged, sizeof(int) * fl.size()));
+        TP_TRY(e->d_flagged.alloc(fl.size()));
         TP_HIP(hipMemcpy(e->d_flagged, fl.data(), sizeof(int) * fl.size(), hipMemcpyHostToDevice));
     }
     e->have_bc = true;

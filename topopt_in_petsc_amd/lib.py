@@ -82,6 +82,7 @@ SYMBOLS = {
     "tp_set_device": (_i, [C.c_int]),
     "tp_malloc": (_i, [C.POINTER(_vp), C.c_size_t]),
     "tp_free": (_i, [_vp]),
+    "tp_device_bytes_live": (C.c_longlong, []),
     "tp_memcpy_h2d": (_i, [_vp, _vp, C.c_size_t]),
     "tp_memcpy_d2h": (_i, [_vp, _vp, C.c_size_t]),
     "tp_sync": (_i, [_vp]),
