@@ -451,6 +451,35 @@ int tp_localvol_constraint(tp_localvol *lv, const double *xPhys, double alpha, d
         double *rhobar,     /* [dev, own elements]; may be NULL */
         double *dgdx);      /* [dev, own elements]; may be NULL */
 
+/* ---- minimum length scale by geometric constraints (no reference counterpart; Zhou, Lazarov, Wang, Sigmund 2015) ---- */
+/* Two scalar constraints on the filtered field rt = xTilde and the projected field rb = xPhys, one for the solid phase and
+ * one for the void phase; no solve.  With e+_a / e-_a the neighbours of element e along axis a, clamped at the DOMAIN boundary
+ * (at a slab border the neighbour is the other rank's element), h_a the spacing and n the GLOBAL element count:
+ *   d_{a,e} = rt[e+_a] - rt[e-_a],  G_e = sum_a (d_{a,e} / (2 h_a))^2,  E_e = exp(-c G_e)        (c in units of length^2)
+ *   solid: a = rb, m = min(rt - eta_s, 0);   void: a = 1 - rb, m = min(eta_v - rt, 0)
+ *   T_e = a_e E_e m_e^2,  S = sum_e T_e over all ranks,  g = S / (n eps) - 1
+ * dg_* receive the TOTAL derivative dg / d xTilde: the projection's H' (the parameters tp_filter_project was called with; proj = 0:
+ * rb = rt, H' = 1) and the stencil's transpose are inside, so the rows go back through tp_filter_gradients_from_tilde and not
+ * through tp_filter_gradients.  kinds: 1 solid | 2 void; a call that asks for one kind writes only that one (g[0], S[0], dg_solid:
+ * solid; g[1], S[1], dg_void: void).  All arrays [dev, own elements].  S is summed layer by layer in ascending global z: g and
+ * every bit of the gradients do not depend on the number of slabs, and two calls give the same bits.  On more than one rank slabs
+ * of fewer than 2 layers are TP_ERR_ARG at creation.  TP_ERR_ARG, before the handle is used, for a NULL handle, xTilde or xPhys,
+ * kinds outside 1..3, c < 0, eps <= 0, any non-finite parameter, eta_s or eta_v outside (0, 1), proj with beta <= 0 or eta
+ * outside [0, 1]. */
+typedef struct tp_lengthscale tp_lengthscale;
+int tp_lengthscale_create(tp_lengthscale **ls, tp_grid *g);
+int tp_lengthscale_destroy(tp_lengthscale *ls);              /* NULL: TP_OK */
+int tp_lengthscale_constraints(tp_lengthscale *ls, const double *xTilde, const double *xPhys,
+                               int proj, double beta, double eta,
+                               double c, double eta_s, double eta_v, double eps, int kinds /* 1 solid | 2 void */,
+                               double *g /*[2], host; may be NULL*/, double *S /*[2], host; may be NULL*/,
+                               double *dg_solid, double *dg_void /* d g / d xTilde, either may be NULL */);
+/* T_e of the last call, own elements; either may be NULL */
+int tp_lengthscale_get_terms(tp_lengthscale *ls, double *T_solid, double *T_void);
+/* rows[i] <- (d xTilde / d x)^T rows[i], i < m, in place: the filter's transpose with no projection chain (types 1, 2).
+ * TP_ERR_ARG for filter type 0, whose "gradient" is a heuristic on dfdx and not a transpose. */
+int tp_filter_gradients_from_tilde(tp_filter *f, const double *x, int m, double **rows);
+
 /* ---- overhang (self-support) filter (no reference counterpart; Langelaar 2016 / 2017) ---- */
 /* A "printed" density xi built from the blueprint density x layer by layer from the baseplate: every element takes the smooth
  * minimum of its own density and the smooth maximum of the five elements that support it in the layer below (itself and its

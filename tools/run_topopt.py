@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """End-to-end run of the reference's optimisation loop on the MI355X path.
-usage: run_topopt.py [--loadcase top[:weight]]... [--stress-limit L [--stress-p P] [--stress-q q]] [--local-volume ALPHA:R] [--overhang +z|-z|+y|-y] [--self-weight bx,by,bz[:xlow] [--no-point-load]] ex ey ez nlvls n_iter [filter [nsmooth ncoarse]]
+usage: run_topopt.py [--loadcase top[:weight]]... [--stress-limit L [--stress-p P] [--stress-q q]] [--local-volume ALPHA:R] [--overhang +z|-z|+y|-y] [--self-weight bx,by,bz[:xlow] [--no-point-load]] [--length-scale both|solid|void[:C]] ex ey ez nlvls n_iter [filter [nsmooth ncoarse]]
 (e.g. 128 128 128 5 20 1 2 45: the cycle of bench.py; --loadcase top:0.5 adds the line load on the upper edge as a second load
 case of weight 0.5 -- the objective becomes the weighted sum of the cases' compliances; --stress-limit L holds the von Mises
 p-norm of load case 0 below L as a second constraint, exponent --stress-p (8), stress relaxation x^q with --stress-q (0.5); --local-volume ALPHA:R holds the mean density in a ball of
@@ -8,7 +8,8 @@ radius R (a length, the element size is 1/ey) around every element below ALPHA t
 the last constraint; --overhang DIR evaluates every response on the printed density of a part built layer by layer along DIR, the
 overhang filter of DESIGN 4.11; --self-weight bx,by,bz[:xlow] adds the structure's own weight, a body force (per unit volume at full
 density) that moves with the design, the mass of elements below xlow (0.1) damped, DESIGN 4.12 -- with --no-point-load it is the only
-load)"""
+load; --length-scale KINDS[:C] holds a minimum length scale of the solid and / or the void phase by the geometric constraints of
+DESIGN 4.13 as the last constraints, decay C in length^2 (default rmin^4 / h^2), with the Heaviside projection switched on)"""
 import os
 import sys
 
@@ -71,11 +72,17 @@ if no_point_load:
     if not body:
         sys.exit("--no-point-load needs --self-weight")
     body["point_load"] = False
+length_scale, length = _last("--length-scale"), {}
+if length_scale is not None:
+    kinds, _, cval = length_scale.partition(":")
+    if kinds not in ("both", "solid", "void"):
+        sys.exit("--length-scale needs both, solid or void, optionally :C, got %r" % length_scale)
+    length = dict(length_scale=kinds, length_scale_c=float(cval) if cval else None, projectionFilter=True)
 ex, ey, ez, nlv, nit = [int(v) for v in sys.argv[1:6]]
 flt = int(sys.argv[6]) if len(sys.argv) > 6 else 1
 h = 1.0 / ey
 opt = tp.TopOpt(nxyz=(ex + 1, ey + 1, ez + 1), xc=(0, ex * h, 0, 1, 0, ez * h), nlvls=nlv, rmin=2.56 * h, filter=flt,
-                loadcases=loadcases or None, **stress, **local, overhang=overhang, **body,
+                loadcases=loadcases or None, **stress, **local, overhang=overhang, **body, **length,
                 solver=tp.SolverOptions(nlvls=nlv, **(dict(nsmooth=int(sys.argv[7]), ncoarse=int(sys.argv[8])) if len(sys.argv) > 8 else {})))
 print("# %dx%dx%d elements, %d DOF, %d MG levels, filter %d, rmin %.4f" % (ex, ey, ez, 3 * (ex + 1) * (ey + 1) * (ez + 1), nlv, flt, 2.56 * h))
 for it in range(nit):
@@ -90,5 +97,9 @@ for it in range(nit):
         print("Overhang:      build %s, mean(xPhys - xPrint): %f" % (overhang, r["print_loss"]), flush=True)
     if "body_share" in r:
         print("Self-weight:   b: %s, x_low: %g, body load's share of the compliance: %f" % (",".join("%g" % v for v in opt.body_force), opt.body_force_xlow, r["body_share"]), flush=True)
+    if "gx_solid" in r:
+        print("Length scale:  c: %g, S: %s | gx[%s]: %s"
+              % (opt.length_scale_c, " ".join("%e" % r[k] for k in ("length_S_solid", "length_S_void") if r[k] is not None),
+                 ",".join(str(k) for k in opt._k_length), " ".join("%f" % r[k] for k in ("gx_solid", "gx_void") if r[k] is not None)), flush=True)
     if "gx_local" in r:
         print("Local volume:  p-norm: %f, max: %f, gx[%d]: %f" % (r["local_pnorm"], r["local_max"], opt.m - 1, r["gx_local"]), flush=True)

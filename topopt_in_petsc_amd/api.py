@@ -769,6 +769,13 @@ class Filter:
         _chk(self.L.tp_filter_gradients(self.handle, _ptr(x), _ptr(xTilde), _ptr(dfdx), len(dgdx), arr,
                                         int(projectionFilter), beta, eta), "tp_filter_gradients")
 
+    def GradientsFromTilde(self, x, rows):
+        """every tensor of the list becomes (d xTilde / d x)^T times itself, in place: the filter's transpose alone, for
+        gradients taken with respect to xTilde (LengthScale); no projection chain.  Filter type 0: TP_ERR_ARG"""
+        arr = (C.c_void_p * max(len(rows), 1))(*[_ptr(r) for r in rows])
+        _chk(self.L.tp_filter_gradients_from_tilde(self.handle, _ptr(x), len(rows), arr), "tp_filter_gradients_from_tilde")
+        return rows
+
     def MultH(self, x, y):
         """y = H x with the cone weights (MatMult(H, ...), Filter.cc:68, :173-189), no division by Hs"""
         _chk(self.L.tp_filter_mult_h(self.handle, _ptr(x), _ptr(y)), "tp_filter_mult_h")
@@ -900,6 +907,50 @@ class LocalVolume:
         _chk(self.L.tp_localvol_constraint(self.handle, _ptr(xPhys), alpha, p, C.byref(g), C.byref(pn), C.byref(mx),
                                            _ptr(rhobar), _ptr(dgdx)), "tp_localvol_constraint")
         return g.value, pn.value, mx.value
+
+
+class LengthScale:
+    """Minimum length scale by geometric constraints (tp_lengthscale): one constraint for the solid and one for the void phase
+    on the filtered field xTilde and the projected field xPhys, g = S / (n eps) - 1 with S = sum_e a_e exp(-c G_e) m_e^2."""
+    KINDS = {"solid": 1, "void": 2, "both": 3}
+
+    def __init__(self, grid):
+        self.grid, self.L = grid, grid.L
+        self.handle = C.c_void_p()
+        _chk(self.L.tp_lengthscale_create(C.byref(self.handle), grid.handle), "tp_lengthscale_create")
+        grid._adopt(self)
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.L.tp_lengthscale_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def Constraints(self, xTilde, xPhys, c, eta_s=0.75, eta_v=0.25, eps=1e-2, kinds="both", projectionFilter=False, beta=0.1,
+                    eta=0.0, dg_solid=None, dg_void=None):
+        """-> dict(g_solid, g_void, S_solid, S_void), None for a kind that was not asked for; dg_solid / dg_void receive
+        dg / dxTilde (the projection's derivative inside: they go back through Filter.GradientsFromTilde), where given.
+        projectionFilter, beta, eta: what FilterProject was called with"""
+        if kinds not in self.KINDS:
+            raise ValueError("kinds must be one of %s, got %r" % (", ".join(sorted(self.KINDS)), kinds))
+        k = self.KINDS[kinds]
+        g, S = (C.c_double * 2)(), (C.c_double * 2)()
+        _chk(self.L.tp_lengthscale_constraints(self.handle, _ptr(xTilde), _ptr(xPhys), int(projectionFilter), beta, eta, c, eta_s,
+                                               eta_v, eps, k, g, S, _ptr(dg_solid), _ptr(dg_void)), "tp_lengthscale_constraints")
+        return dict(g_solid=g[0] if k & 1 else None, g_void=g[1] if k & 2 else None,
+                    S_solid=S[0] if k & 1 else None, S_void=S[1] if k & 2 else None)
+
+    def Terms(self, solid=True, void=True):
+        """(T_solid, T_void) of the last call, own elements; None for one that was not asked for"""
+        ts = self.grid.elem_vec() if solid else None
+        tv = self.grid.elem_vec() if void else None
+        _chk(self.L.tp_lengthscale_get_terms(self.handle, _ptr(ts), _ptr(tv)), "tp_lengthscale_get_terms")
+        return ts, tv
 
 
 class Overhang:

@@ -786,6 +786,17 @@ extern "C" int tp_filter_gradients(tp_filter *f, const double *x, const double *
     return TP_OK;
 }
 
+// rows[i] <- (d xTilde / d x)^T rows[i]: the filter's transpose alone, for gradients taken with respect to xTilde itself
+// (lengthscale.h) -- no projection chain.  The sensitivity filter's "gradient" is a heuristic on dfdx, not a transpose.
+extern "C" int tp_filter_gradients_from_tilde(tp_filter *f, const double *x, int m, double **rows) {
+    if (!f || !x || m < 0 || (m > 0 && !rows)) return TP_ERR_ARG;
+    if (f->type == 0) return TP_ERR_ARG;
+    for (int i = 0; i < m; i++)
+        if (!rows[i]) return TP_ERR_ARG;
+    for (int i = 0; i < m; i++) TP_TRY(filter_gradient_one(f, x, rows[i]));
+    return TP_OK;
+}
+
 extern "C" int tp_filter_mnd(tp_filter *f, const double *x, double *mnd) {
     tp_grid *g = f->grid;
     const int nb = grid_for(f->nel, MAX_RED_BLOCKS);

@@ -1400,6 +1400,11 @@ extern "C" int tp_elasticity_last_op_form(const tp_elasticity *e, int *form4) {
 #include "localvol.h"
 
 // ===========================================================================
+// minimum length scale: geometric constraints on the filtered and projected fields
+// ===========================================================================
+#include "lengthscale.h"
+
+// ===========================================================================
 // overhang (self-support) filter: layer sweeps along the build axis
 // ===========================================================================
 #include "overhang.h"

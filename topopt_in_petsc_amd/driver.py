@@ -16,7 +16,7 @@ import torch
 from . import mpiio
 import ctypes as C
 
-from .api import Filter, Grid, LinearElasticity, LocalVolume, MMA, Overhang, SolverOptions, _chk, _ptr, check_body_force
+from .api import Filter, Grid, LengthScale, LinearElasticity, LocalVolume, MMA, Overhang, SolverOptions, _chk, _ptr, check_body_force
 
 
 @dataclass
@@ -72,8 +72,8 @@ class TopOpt:
     stress_q: float = 0.5
     stress_case: int = 0
     # local volume constraint: the p-norm (exponent local_volume_p) of the mean density in a ball of radius local_volume_R
-    # around every element held below local_volume as the LAST MMA constraint g = pn / local_volume - 1 (None: none, nothing
-    # changes); the constraints are ordered [volume, stress?, local]
+    # around every element held below local_volume as an MMA constraint g = pn / local_volume - 1 behind the stress constraint
+    # (None: none, nothing changes); the constraints are ordered [volume, stress?, local?, solid?, void?]
     local_volume: float = None
     local_volume_R: float = None
     local_volume_p: float = 16.0
@@ -87,6 +87,17 @@ class TopOpt:
     body_force: tuple = None
     body_force_xlow: float = 0.1
     point_load: bool = True
+    # minimum length scale by geometric constraints: "both", "solid" or "void" adds one MMA constraint per phase
+    # behind every other one, g = S / (n length_scale_eps) - 1 on the blueprint (xTilde, xPhys) -- not on xPrint.  length_scale_c:
+    # the decay c of exp(-c |grad xTilde|^2) in length^2 (None: rmin^4 / h_min^2, the paper's c = r^4 for r in elements);
+    # length_scale_eta: the thresholds (eta_s, eta_v), 0.75 / 0.25 for a length scale equal to the filter size; before iteration
+    # length_scale_start the values are recorded but MMA sees g = -1 and a zero row; length_scale_eps = 1e-2 is the value of a
+    # measured sweep at which MMA reached feasibility with a structure left, 1e-6 .. 1e-3 did not (None: none, nothing changes)
+    length_scale: str = None
+    length_scale_c: float = None
+    length_scale_eta: tuple = (0.75, 0.25)
+    length_scale_eps: float = 1e-2
+    length_scale_start: int = 1
     history: list = field(default_factory=list)
 
     def __post_init__(self):
@@ -98,6 +109,19 @@ class TopOpt:
             check_body_force((0.0, 0.0, 0.0), self.body_force_xlow)
             if not self.point_load:
                 raise ValueError("point_load=False needs a body_force: the structure would carry no load")
+        if self.length_scale is not None:
+            if self.length_scale not in LengthScale.KINDS:
+                raise ValueError("length_scale must be None or one of %s, got %r" % (", ".join(sorted(LengthScale.KINDS)), self.length_scale))
+            if self.filter == 0:
+                raise ValueError("length_scale needs a density or PDE filter: the sensitivity filter (filter=0) has no transpose")
+            if self.length_scale_c is not None and not self.length_scale_c > 0.0:
+                raise ValueError("length_scale_c must be positive")
+            if not self.length_scale_eps > 0.0:
+                raise ValueError("length_scale_eps must be positive")
+            if len(self.length_scale_eta) != 2 or not all(0.0 < v < 1.0 for v in self.length_scale_eta):
+                raise ValueError("length_scale_eta: two thresholds inside (0, 1), got %r" % (self.length_scale_eta,))
+            if not self.length_scale_start >= 1:
+                raise ValueError("length_scale_start must be at least 1")
         if self.stress_limit is not None:
             if not self.stress_limit > 0.0:
                 raise ValueError("stress_limit must be positive")
@@ -113,6 +137,13 @@ class TopOpt:
         nx, ny, nz = self.nxyz
         h = ((self.xc[1] - self.xc[0]) / (nx - 1), (self.xc[3] - self.xc[2]) / (ny - 1),
              (self.xc[5] - self.xc[4]) / (nz - 1))
+        self._k_length = ()
+        if self.length_scale is not None:   # the rows behind every other one
+            nk = 2 if self.length_scale == "both" else 1
+            self._k_length = tuple(range(self.m, self.m + nk))
+            self.m += nk
+            if self.length_scale_c is None:
+                self.length_scale_c = self.rmin ** 4 / min(h) ** 2
         self.grid = Grid(nx, ny, nz, h, rank=self.rank, nranks=self.nranks)
         so = self.solver or SolverOptions(nlvls=self.nlvls, nu=self.nu)
         self.physics = LinearElasticity(self.grid, so)
@@ -132,6 +163,7 @@ class TopOpt:
         self.filt = Filter(self.grid, self.filter, self.rmin)
         self.localvol = LocalVolume(self.grid, self.local_volume_R) if self.local_volume is not None else None
         self.overhang_filter = Overhang(self.grid, self.overhang) if self.overhang is not None else None
+        self.lengthscale = LengthScale(self.grid) if self.length_scale is not None else None
         g = self.grid
         # TopOpt.cc:362-381: all design fields start at volfrac
         self.x = g.elem_vec(self.volfrac)
@@ -204,9 +236,26 @@ class TopOpt:
             g_local, pn_local, rb_max = self.localvol.Constraint(self.xPrint, self.local_volume, self.local_volume_p,
                                                                  dgdx=self.dgdx[self._k_local])
             gxs.append(g_local)
+        rows = self.dgdx   # what goes back through the overhang filter and the projection: every row but the length scale's
+        if self.lengthscale is not None:    # on the blueprint (xTilde, xPhys); d/dxTilde, the projection's derivative inside
+            rows, lrows = self.dgdx[:self._k_length[0]], [self.dgdx[k] for k in self._k_length]
+            solid, void = self.length_scale != "void", self.length_scale != "solid"
+            ls = self.lengthscale.Constraints(self.xTilde, self.xPhys, self.length_scale_c, self.length_scale_eta[0],
+                                              self.length_scale_eta[1], self.length_scale_eps, self.length_scale,
+                                              self.projectionFilter, self.beta, self.eta,
+                                              dg_solid=lrows[0] if solid else None, dg_void=lrows[-1] if void else None)
+            g_length = [ls[k] for k, on in (("g_solid", solid), ("g_void", void)) if on]
+            if self.itr < self.length_scale_start:   # recorded, but not yet held
+                gxs.extend(-1.0 for _ in g_length)
+                for r in lrows:
+                    r.zero_()
+            else:
+                gxs.extend(g_length)
         if self.overhang_filter is not None:   # d/dxPrint -> d/dxPhys, all of them in one sweep
-            self.overhang_filter.Adjoint([self.dfdx] + self.dgdx)
-        self.filt.Gradients(self.x, self.xTilde, self.dfdx, self.dgdx, self.projectionFilter, self.beta, self.eta)
+            self.overhang_filter.Adjoint([self.dfdx] + rows)
+        self.filt.Gradients(self.x, self.xTilde, self.dfdx, rows, self.projectionFilter, self.beta, self.eta)
+        if self.lengthscale is not None:
+            self.filt.GradientsFromTilde(self.x, lrows)
         self.mma.SetOuterMovelimit(self.Xmin, self.Xmax, self.movlim, self.x, self.xmin, self.xmax)  # :81
         self.mma.Update(self.x, self.dfdx, gxs, self.dgdx, self.xmin, self.xmax)                 # :85
         if self.kkt:
@@ -232,6 +281,9 @@ class TopOpt:
             rec["stress_pnorm"], rec["stress_max"], rec["gx_stress"], rec["ksp_its_adjoint"] = pnorm, vm_max, gxs[1], its_adj
         if self.localvol is not None:
             rec["gx_local"], rec["local_pnorm"], rec["local_max"] = g_local, pn_local, rb_max
+        if self.lengthscale is not None:
+            rec["gx_solid"], rec["gx_void"] = ls["g_solid"], ls["g_void"]
+            rec["length_S_solid"], rec["length_S_void"] = ls["S_solid"], ls["S_void"]
         if self.overhang_filter is not None:
             rec["print_loss"] = self._mean(self.xPhys - self.xPrint)
         if self.body_force is not None:

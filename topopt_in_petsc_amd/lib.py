@@ -189,6 +189,11 @@ SYMBOLS = {
     "tp_overhang_adjoint": (_i, [_vp, _i, C.POINTER(_vp)]),
     "tp_overhang_last_chunk": (_i, [_vp]),
     "tp_localvol_constraint": (_i, [_vp, _vp, _d, _d, C.POINTER(_d), C.POINTER(_d), C.POINTER(_d), _vp, _vp]),
+    "tp_lengthscale_create": (_i, [C.POINTER(_vp), _vp]),
+    "tp_lengthscale_destroy": (_i, [_vp]),
+    "tp_lengthscale_constraints": (_i, [_vp, _vp, _vp, _i, _d, _d, _d, _d, _d, _d, _i, C.POINTER(_d), C.POINTER(_d), _vp, _vp]),
+    "tp_lengthscale_get_terms": (_i, [_vp, _vp, _vp]),
+    "tp_filter_gradients_from_tilde": (_i, [_vp, _vp, _i, C.POINTER(_vp)]),
 }
 
 
