@@ -1,10 +1,14 @@
 // mma_probe.cc -- the device MMA through the C++ mirror (topopt_host.h) on the synthetic problem of ref_mma_driver.cc,
 // on one or more z-slab ranks (`slabrun -n N [--same-device] mma_probe ...`): prints KKTresidual's norms, first before
 // any Update (lam = y = z = 0: the inputs are the same on every rank count, bit for bit), then after every Update.
-//   mma_probe ex ey ez m iters [a=. c=. d=. asym=i,dec,inc robust=0|1 conmod=0|1 box=1]
+//   mma_probe ex ey ez m iters [a=. c=. d=. asym=i,dec,inc robust=0|1 conmod=0|1 box=1 dump=PATH]
 // Output (rank 0): "MMA_PROBE kkt <k> <norm2 %.17e> <normInf %.17e>", k = 0 before the first Update.
+// dump=PATH: after every Update each rank appends its slab of x, raw float64, to PATH.<rank> (the slabs in rank order are
+// the global vector), and rank 0 prints "MMA_PROBE lam <k> <lam_0 %.17e> ... <lam_m-1>".
 #include <cmath>
+#include <cstdio>
 #include <cstring>
+#include <string>
 
 #include "slab_comm.h"
 #include "topopt_host.h"
@@ -30,6 +34,7 @@ int main(int argc, char **argv) {
     bool acd = false, asym = false, box = false;
     double av = 0.0, cv = 1000.0, dv = 0.0, ai = 0.5, ad = 0.7, ainc = 1.2;
     int robust = 0, conmod = 0;
+    std::string dump;
     for (int t = 6; t < argc; t++) {
         const char *s = argv[t];
         if (!strncmp(s, "a=", 2)) acd = true, av = atof(s + 2);
@@ -41,6 +46,7 @@ int main(int argc, char **argv) {
         } else if (!strncmp(s, "robust=", 7)) robust = atoi(s + 7);
         else if (!strncmp(s, "conmod=", 7)) conmod = atoi(s + 7);
         else if (!strncmp(s, "box=", 4)) box = atoi(s + 4) != 0;
+        else if (!strncmp(s, "dump=", 5)) dump = s + 5;
         else return 2;
     }
     const int nx = ex + 1, ny = ey + 1, nz = ez + 1;
@@ -72,6 +78,11 @@ int main(int argc, char **argv) {
     mma->SetRobustAsymptotesType(robust);
     mma->ConstraintModification(conmod ? PETSC_TRUE : PETSC_FALSE);
     std::vector<double> gx((size_t)m);
+    FILE *df = nullptr;
+    if (!dump.empty()) {
+        df = fopen((dump + "." + std::to_string(sc.rank)).c_str(), "wb");
+        if (!df) return 3;
+    }
     for (int k = 0; k <= iters; k++) {
         double *xp, *dfp;
         VecGetArray(x, &xp);
@@ -109,12 +120,27 @@ int main(int argc, char **argv) {
         if (k > 0) {
             ierr = mma->Update(x, dfdx, gx.data(), dgdx.data(), xmin, xmax);
             CHKERRQ(ierr);
+            if (df) {
+                VecGetArray(x, &xp);
+                const size_t wrote = fwrite(xp, sizeof(double), (size_t)nloc, df);
+                VecRestoreArray(x, &xp);
+                if (wrote != (size_t)nloc) return 3;
+                std::vector<double> lam((size_t)m);
+                ierr = mma->GetState(lam.data(), nullptr, nullptr);
+                CHKERRQ(ierr);
+                if (root) {
+                    printf("MMA_PROBE lam %d", k);
+                    for (double l : lam) printf(" %.17e", l);
+                    printf("\n");
+                }
+            }
         }
         double n2 = 0.0, nI = 0.0;
         ierr = mma->KKTresidual(x, dfdx, gx.data(), dgdx.data(), xmin, xmax, &n2, &nI);
         CHKERRQ(ierr);
         if (root) printf("MMA_PROBE kkt %d %.17e %.17e\n", k, n2, nI);
     }
+    if (df && fclose(df)) return 3;
     delete mma;
     for (Vec *v : {&x, &dfdx, &xmin, &xmax}) VecDestroy(v);
     for (Vec &v : dgdx) VecDestroy(&v);

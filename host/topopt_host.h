@@ -199,6 +199,9 @@ class MMA {
         tp_mma_design_change(h, x->d, xold->d, &ch);
         return ch;
     }
+    // the dual point of the last Update (lam: m values) and the number of Updates; null = not wanted.  Not in MMA.h,
+    // where lam is a private member: for probes and tests.
+    PetscErrorCode GetState(PetscScalar *lam, PetscScalar *z, PetscInt *k) { return tp_mma_get_state(h, lam, z, k); }
     PetscErrorCode err = 0;
     int inner = 0;
 

@@ -505,7 +505,8 @@ int tp_overhang_last_chunk(const tp_overhang *ov);              /* layers per la
 /* ---- MMA optimizer step on the device (MMA.cc) ------------ */
 typedef struct tp_mma tp_mma;
 /* MMA::MMA(n, m, x) (MMA.cc:108-190): a = 0, c = 1000, d = 0, asymptote factors 0.5 / 0.7 / 1.2.
- * n_local = own design variables of this rank, n_global = all of them; x [dev, n_local]. */
+ * n_local = own design variables of this rank, n_global = all of them; x [dev, n_local].
+ * TP_ERR_ARG unless 1 <= m <= 7: the m + m^2 sums of a dual Newton step come back in one 64-value host buffer. */
 int tp_mma_create(tp_mma **mma, tp_grid *g, long n_local, long n_global, int m, const double *x);
 int tp_mma_destroy(tp_mma *mma);
 /* SetOuterMovelimit (MMA.cc:386-405) */

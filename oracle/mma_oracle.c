@@ -6,7 +6,9 @@
  *   GenSub :522-649, SolveDIP :651-688, XYZofLAMBDA :690-740, DualGrad :742-777,
  *   DualHess :779-880, DualLineSearch :882-900, DualResidual :902-946,
  *   Factorize/Solve :948-981, SetOuterMovelimit :386-405, DesignChange :407-426,
- *   KKTresidual :428-496.
+ *   KKTresidual :428-496, and the settings: the a/c/d constructors :195-242,
+ *   SetAsymptotes :362-370, SetRobustAsymptotesType :372-384 (GenSub :574-589),
+ *   ConstraintModification (GenSub :604-608).
  * The reference ships no test for MMA and needs PETSc Vecs to run: parity of this
  * restatement is anchored on optimality/feasibility properties (tests/test_mma.py).
  */
@@ -23,6 +25,7 @@ typedef struct {
     double *a, *c, *d, *y, *lam, *mu, *b, *grad, *s, *Hess;
     double z;
     double *L, *U, *alpha, *beta, *p0, *q0, *pij, *qij, *xo1, *xo2; /* pij/qij: m blocks of n */
+    int robust, conmod; /* SetRobustAsymptotesType (0 | 1), ConstraintModification */
     int dev_order; /* 0: the reference's left-to-right sums and pow(); > 0: the DEVICE's operation order (workgroups) */
 } orc_mma_t;
 
@@ -48,13 +51,15 @@ static double dev_block_sum(const double *v256) {
     for (int wv = 0; wv < 4; wv++) t += w[wv];
     return t;
 }
-static double dev_order_sum(const double *term, long n, int nb) {
+/* w terms per element, added one after the other by the element's thread (w = 3: k_mma_kkt's three squares) */
+static double dev_order_sum_w(const double *term, long n, int w, int nb) {
     double *part = (double *)calloc((size_t)nb, sizeof(double));
     for (int b = 0; b < nb; b++) {
         double v[256];
         for (int t = 0; t < 256; t++) {
             double acc = 0.0;
-            for (long i = (long)b * 256 + t; i < n; i += (long)nb * 256) acc += term[i];
+            for (long i = (long)b * 256 + t; i < n; i += (long)nb * 256)
+                for (int q = 0; q < w; q++) acc += term[i * w + q];
             v[t] = acc;
         }
         part[b] = dev_block_sum(v);
@@ -69,7 +74,7 @@ static double dev_order_sum(const double *term, long n, int nb) {
     return dev_block_sum(v);
 }
 static double sum_terms(const orc_mma_t *M, const double *term, long n) {
-    if (M->dev_order > 0) return dev_order_sum(term, n, M->dev_order);
+    if (M->dev_order > 0) return dev_order_sum_w(term, n, 1, M->dev_order);
     double sacc = 0.0;
     for (long i = 0; i < n; i++) sacc += term[i];
     return sacc;
@@ -117,6 +122,37 @@ ORC_API orc_mma_t *orc_mma_create(long n, int m, const double *x) {
 }
 /* nb = number of 256-thread workgroups of the device kernels (csrc/mma.h: grid_for(n, 1024)); 0 = reference order */
 ORC_API void orc_mma_set_device_order(orc_mma_t *M, int nb) { M->dev_order = nb; }
+/* the a/c/d constructors (MMA.cc:195-242): per constraint; a null pointer keeps what is there.  d is kept like the
+ * reference keeps it; its solver never reads it. */
+ORC_API void orc_mma_set_subproblem(orc_mma_t *M, const double *a, const double *c, const double *d) {
+    for (int j = 0; j < M->m; j++) {
+        if (a) M->a[j] = a[j];
+        if (c) M->c[j] = c[j];
+        if (d) M->d[j] = d[j];
+    }
+}
+/* SetAsymptotes (MMA.cc:362-370) */
+ORC_API void orc_mma_set_asymptotes(orc_mma_t *M, double init, double decrease, double increase) {
+    M->asyminit = init;
+    M->asymdec  = decrease;
+    M->asyminc  = increase;
+}
+/* SetRobustAsymptotesType (MMA.cc:372-384): anything but 0 or 1 leaves type 0 and returns non-zero */
+ORC_API int orc_mma_set_robust_asymptotes_type(orc_mma_t *M, int val) {
+    const int ok = val == 0 || val == 1;
+    M->robust = ok ? val : 0;
+    return ok ? 0 : 1;
+}
+/* ConstraintModification (MMA.h:53) */
+ORC_API void orc_mma_constraint_modification(orc_mma_t *M, int on) { M->conmod = on ? 1 : 0; }
+/* what GenSub left: the move limits of the sub-problem and the two previous iterates (null = not wanted) */
+ORC_API void orc_mma_get_subproblem(orc_mma_t *M, double *alpha, double *beta, double *xo1, double *xo2) {
+    size_t nb = sizeof(double) * (size_t)M->n;
+    if (alpha) memcpy(alpha, M->alpha, nb);
+    if (beta) memcpy(beta, M->beta, nb);
+    if (xo1) memcpy(xo1, M->xo1, nb);
+    if (xo2) memcpy(xo2, M->xo2, nb);
+}
 ORC_API void orc_mma_destroy(orc_mma_t *M) {
     if (!M) return;
     free(M->a); free(M->c); free(M->d); free(M->y); free(M->lam); free(M->mu); free(M->b); free(M->grad); free(M->s);
@@ -167,10 +203,28 @@ static void gensub(orc_mma_t *M, const double *xv, const double *dfdx, const dou
             M->L[i] = xv[i] - gamma * (M->xo1[i] - M->L[i]);
             M->U[i] = xv[i] + gamma * (M->U[i] - M->xo1[i]);
             double xmi = dmax(1.0e-5, xmax[i] - xmin[i]);
-            M->L[i] = dmax(M->L[i], xv[i] - 10.0 * xmi);
-            M->L[i] = dmin(M->L[i], xv[i] - 0.01 * xmi);
-            M->U[i] = dmax(M->U[i], xv[i] + 0.01 * xmi);
-            M->U[i] = dmin(M->U[i], xv[i] + 10.0 * xmi);
+            if (M->robust == 0) {
+                M->L[i] = dmax(M->L[i], xv[i] - 10.0 * xmi);
+                M->L[i] = dmin(M->L[i], xv[i] - 0.01 * xmi);
+                M->U[i] = dmax(M->U[i], xv[i] + 0.01 * xmi);
+                M->U[i] = dmin(M->U[i], xv[i] + 10.0 * xmi);
+            } else {
+                /* type 1 (:574-589): wider clamps, and a variable outside its box by more than 1e-5 gets asymptotes
+                 * centred on it, as far away as the box's far side over 0.9 */
+                M->L[i] = dmax(M->L[i], xv[i] - 100.0 * xmi);
+                M->L[i] = dmin(M->L[i], xv[i] - 1.0e-4 * xmi);
+                M->U[i] = dmax(M->U[i], xv[i] + 1.0e-4 * xmi);
+                M->U[i] = dmin(M->U[i], xv[i] + 100.0 * xmi);
+                double xlo = xmin[i] - 1.0e-5, xhi = xmax[i] + 1.0e-5;
+                if (xv[i] < xlo) {
+                    M->L[i] = xv[i] - (xhi - xv[i]) / 0.9;
+                    M->U[i] = xv[i] + (xhi - xv[i]) / 0.9;
+                }
+                if (xv[i] > xhi) {
+                    M->L[i] = xv[i] - (xv[i] - xlo) / 0.9;
+                    M->U[i] = xv[i] + (xv[i] - xlo) / 0.9;
+                }
+            }
         }
     }
     const double feps = 1.0e-6;
@@ -185,8 +239,13 @@ static void gensub(orc_mma_t *M, const double *xv, const double *dfdx, const dou
             double g = dgdx[(size_t)j * n + i];
             dp = dmax(0.0, g);
             dm = dmax(0.0, -1.0 * g);
-            M->pij[(size_t)j * n + i] = pow(Ui - xv[i], 2.0) * dp; /* constraintModification = false */
-            M->qij[(size_t)j * n + i] = pow(xv[i] - Li, 2.0) * dm;
+            if (M->conmod) { /* :604-608: the constraints get the objective's convexifying terms */
+                M->pij[(size_t)j * n + i] = pow(Ui - xv[i], 2.0) * (dp + 0.001 * dabs(g) + 0.5 * feps / (Ui - Li));
+                M->qij[(size_t)j * n + i] = pow(xv[i] - Li, 2.0) * (dm + 0.001 * dabs(g) + 0.5 * feps / (Ui - Li));
+            } else {
+                M->pij[(size_t)j * n + i] = pow(Ui - xv[i], 2.0) * dp;
+                M->qij[(size_t)j * n + i] = pow(xv[i] - Li, 2.0) * dm;
+            }
         }
     }
     double *term = (double *)malloc(sizeof(double) * (size_t)n);
@@ -367,6 +426,9 @@ ORC_API void orc_mma_kkt(orc_mma_t *M, const double *x, const double *dfdx, cons
     long n = M->n;
     int m  = M->m;
     double n2 = 0.0, nI = 0.0;
+    /* device order: the three squares of an element go into its thread's sum one after the other (k_mma_kkt), the
+     * threads and workgroups are then added as in every other sum (k_sum_max_final) */
+    double *sq = M->dev_order > 0 ? (double *)malloc(sizeof(double) * 3 * (size_t)n) : NULL;
     for (long i = 0; i < n; i++) {
         double ri = dfdx[i];
         for (int j = 0; j < m; j++) ri += M->lam[j] * dgdx[(size_t)j * n + i];
@@ -374,14 +436,21 @@ ORC_API void orc_mma_kkt(orc_mma_t *M, const double *x, const double *dfdx, cons
         if (x[i] < xmin[i] + 1.0e-5 && ri > 0.0) mu_min = ri;
         if (x[i] > xmax[i] - 1.0e-5 && ri < 0.0) mu_max = -ri;
         ri += -mu_min + mu_max;
-        n2 += pow(ri, 2.0);
+        if (sq) sq[3 * i] = ri * ri;
+        else n2 += pow(ri, 2.0);
         nI = dmax(dabs(ri), nI);
         double resi = mu_min * (x[i] - xmin[i]);
-        n2 += pow(resi, 2.0);
+        if (sq) sq[3 * i + 1] = resi * resi;
+        else n2 += pow(resi, 2.0);
         nI = dmax(dabs(resi), nI);
         resi = mu_max * (xmax[i] - x[i]);
-        n2 += pow(resi, 2.0);
+        if (sq) sq[3 * i + 2] = resi * resi;
+        else n2 += pow(resi, 2.0);
         nI = dmax(dabs(resi), nI);
+    }
+    if (sq) {
+        n2 = dev_order_sum_w(sq, n, 3, M->dev_order);
+        free(sq);
     }
     double ri = 0.0;
     for (int j = 0; j < m; j++) ri += M->lam[j] * (M->a[j] * M->z + M->y[j] - fx[j]);

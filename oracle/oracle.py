@@ -106,6 +106,12 @@ def lib():
             L.orc_mma_create.argtypes = [C.c_long, C.c_int, C.c_void_p]
             L.orc_mma_destroy.argtypes = [C.c_void_p]
             L.orc_mma_set_device_order.argtypes = [C.c_void_p, C.c_int]
+            L.orc_mma_set_subproblem.argtypes = [C.c_void_p] * 4
+            L.orc_mma_set_asymptotes.argtypes = [C.c_void_p, c_real, c_real, c_real]
+            L.orc_mma_set_robust_asymptotes_type.restype = C.c_int
+            L.orc_mma_set_robust_asymptotes_type.argtypes = [C.c_void_p, C.c_int]
+            L.orc_mma_constraint_modification.argtypes = [C.c_void_p, C.c_int]
+            L.orc_mma_get_subproblem.argtypes = [C.c_void_p] * 5
             L.orc_mma_get_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
             L.orc_mma_outer_movelimit.argtypes = [C.c_long, c_real, c_real, c_real, C.c_void_p, C.c_void_p,
                                                   C.c_void_p]
@@ -415,11 +421,19 @@ def mnd(x):
 class MMA:
     """oracle MMA (mma_oracle.c); vectors are numpy arrays, dgdx a list of m arrays"""
 
-    def __init__(self, x, m=1):
+    def __init__(self, x, m=1, a=None, c=None, d=None):
+        """a, c, d: the a/c/d constructors (MMA.cc:195-242), each a sequence of m or one number for all j; None keeps
+        the defaults a = 0, c = 1000, d = 0"""
         self.L = lib()
         self.n, self.m = x.size, m
         self.h = self.L.orc_mma_create(self.n, m, _p(f64(x)))
         self.last_inner = 0
+        if a is not None or c is not None or d is not None:
+            acd = [None if v is None else f64(np.full(m, v, dtype=REAL) if np.ndim(v) == 0 else np.asarray(v, dtype=REAL))
+                   for v in (a, c, d)]
+            if any(v is not None and v.size != m for v in acd):
+                raise ValueError("need %d values per penalty number" % m)
+            self.L.orc_mma_set_subproblem(self.h, *[None if v is None else _p(v) for v in acd])
 
     def __del__(self):
         if getattr(self, "h", None):
@@ -431,6 +445,19 @@ class MMA:
         multiplication: for bit-for-bit comparisons with the device; default = the reference's loops and pow()"""
         nb = min(max((self.n + 255) // 256, 1), 1024) if on else 0
         self.L.orc_mma_set_device_order(self.h, nb)
+
+    def SetAsymptotes(self, init, decrease, increase):
+        """MMA::SetAsymptotes (MMA.cc:362-370)"""
+        self.L.orc_mma_set_asymptotes(self.h, init, decrease, increase)
+
+    def SetRobustAsymptotesType(self, val):
+        """MMA::SetRobustAsymptotesType (MMA.cc:372-384): 0 or 1; any other value leaves type 0 and raises"""
+        if self.L.orc_mma_set_robust_asymptotes_type(self.h, int(val)):
+            raise ValueError("robust asymptotes type %r: 0 or 1" % (val,))
+
+    def ConstraintModification(self, conMod):
+        """MMA::ConstraintModification (MMA.h:53)"""
+        self.L.orc_mma_constraint_modification(self.h, 1 if conMod else 0)
 
     def SetOuterMovelimit(self, Xmin, Xmax, movlim, x):
         xmin, xmax = _z(self.n), _z(self.n)
@@ -454,6 +481,18 @@ class MMA:
         z = c_real()
         self.L.orc_mma_get_state(self.h, _p(lam), C.addressof(z), None, None)
         return lam, z.value
+
+    def asymptotes(self):
+        """(L, U) as the last Update left them"""
+        lam, z, Lv, Uv = _z(self.m), c_real(), _z(self.n), _z(self.n)
+        self.L.orc_mma_get_state(self.h, _p(lam), C.addressof(z), _p(Lv), _p(Uv))
+        return Lv, Uv
+
+    def subproblem(self):
+        """(alpha, beta, xo1, xo2) as the last Update left them"""
+        out = [_z(self.n) for _ in range(4)]
+        self.L.orc_mma_get_subproblem(self.h, *[_p(v) for v in out])
+        return tuple(out)
 
     def kkt(self, x, dfdx, fx, dgdx, xmin, xmax):
         n2, ni = c_real(), c_real()

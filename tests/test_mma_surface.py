@@ -325,6 +325,54 @@ def test_kkt_residual_across_slab_ranks():
         assert abs(b[0] / a[0] - 1.0) <= 1e-9 and abs(b[1] / a[1] - 1.0) <= 1e-9, (a, b)
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("m,tokens", [(4, []), (7, ["robust=1", "box=1"])], ids=["m4", "m7-robust-box"])
+def test_many_constraints_across_slab_ranks(orc, tmp_path, m, tokens):
+    """mma_reduce sends its m + m^2 sums through the comm hook 16 at a time: m = 4 (20 values, two chunks) and m = 7 (56
+    values, four chunks) on 1, 2 and 3 slab ranks of one GPU, 16 x 8 x 12, host/mma_probe with dump=.  Against the
+    one-rank run, slabs concatenated in rank order: every iteration's design to 1e-9, lam to 1e-9 of its largest entry
+    (test_mma.py's form of the bound), both KKT norms to 1e-9 relative, and before the first Update normInf exactly and
+    norm2 to 1e-13 -- the bounds the suite holds two summation orders of the same step to.  The one-rank run itself is held
+    to the oracle in reference order at 1e-9, on the problem rebuilt in numpy (numpy's sin / cos against libm's in the last
+    bit of the inputs: no bit-equality asked)."""
+    from test_oracle_mma_settings import run_oracle_synthetic
+    ex, ey, ez, iters = 16, 8, 12, 6
+    n = ex * ey * ez
+    probe = os.path.join(ROOT, "host", "mma_probe")
+    runs = {}
+    for nproc in (1, 2, 3):
+        dump = str(tmp_path / ("x%d" % nproc))
+        r = subprocess.run([os.path.join(ROOT, "host", "slabrun"), "-n", str(nproc), "--same-device", probe, str(ex), str(ey),
+                            str(ez), str(m), str(iters)] + tokens + ["dump=" + dump], capture_output=True, text=True,
+                           timeout=120)
+        assert r.returncode == 0, (nproc, r.stdout[-2000:] + r.stderr[-2000:])
+        lines = r.stdout.splitlines()
+        kkt = np.array([[float(v) for v in l.split()[3:5]] for l in lines if l.startswith("MMA_PROBE kkt ")])
+        lam = np.array([[float(v) for v in l.split()[3:]] for l in lines if l.startswith("MMA_PROBE lam ")])
+        slabs = [np.fromfile("%s.%d" % (dump, rk), dtype=np.float64) for rk in range(nproc)]
+        assert all(s.size % iters == 0 for s in slabs) and sum(s.size for s in slabs) == iters * n, [s.size for s in slabs]
+        xs = np.concatenate([s.reshape(iters, -1) for s in slabs], axis=1)
+        assert kkt.shape == (iters + 1, 2) and lam.shape == (iters, m) and xs.shape == (iters, n)
+        runs[nproc] = (xs, lam, kkt)
+    xs1, lam1, kkt1 = runs[1]
+    for nproc in (2, 3):
+        xs, lam, kkt = runs[nproc]
+        assert kkt[0][1] == kkt1[0][1], (nproc, kkt[0], kkt1[0])
+        assert abs(kkt[0][0] - kkt1[0][0]) <= 1e-13 * kkt1[0][0], (nproc, kkt[0], kkt1[0])
+        dx = float(np.abs(xs - xs1).max())
+        dlam = float((np.abs(lam - lam1).max(axis=1) / np.maximum(np.abs(lam1).max(axis=1), 1.0)).max())
+        dkkt = float(np.abs(kkt[1:] / kkt1[1:] - 1.0).max())
+        print("m = %d, %d ranks against 1: design %.2e, lam %.2e, KKT %.2e" % (m, nproc, dx, dlam, dkkt))
+        assert dx <= 1e-9 and dlam <= 1e-9 and dkkt <= 1e-9, (nproc, dx, dlam, dkkt)
+    xs_o, kkt_o, lam_o = run_oracle_synthetic(orc, n, m, iters, tokens, kkt_before=True)
+    dx = float(np.abs(xs1 - xs_o).max())
+    dlam = float((np.abs(lam1 - lam_o).max(axis=1) / np.maximum(np.abs(lam_o).max(axis=1), 1.0)).max())
+    dkkt = float(np.abs(kkt1 / kkt_o - 1.0).max())
+    print("m = %d, 1 rank against the oracle in reference order: design %.2e, lam %.2e, KKT %.2e" % (m, dx, dlam, dkkt))
+    assert dx <= 1e-9 and dlam <= 1e-9 and dkkt <= 1e-9, (dx, dlam, dkkt)
+    assert not np.array_equal(xs1[0], xs1[-1])
+
+
 _DRIVER_KW = dict(nxyz=(33, 17, 17), nlvls=3, rmin=0.1, volfrac=0.3)
 _RECORD_KEYS = {"itr", "fx", "fx_scaled", "gx", "ch", "mnd", "time", "ksp_its", "ksp_rerr", "mma_inner"}
 
