@@ -320,6 +320,27 @@ int tp_elasticity_body_load(tp_elasticity *e, const double *xPhys /*[dev, own el
 int tp_elasticity_body_sensitivity(tp_elasticity *e, int ncase, const double *const *V /*host array of [dev] pointers*/,
                             const double *w /*host, NULL = all 1*/, const double *xPhys, const double *b3, double x_low,
                             double scale, double *dfdx /*[dev, own elements], added to*/);
+/* The consistent mass matrix as an operator, and the mass half of an eigenvalue's design sensitivity (free vibration:
+ * A phi = lambda B phi with A = N K N + (I - N), what tp_elasticity_apply applies, and B = N M N).
+ *   M_e = rho0 m(x_e) V_e (M8 (x) I_3),  M8[a,b] = (1/8) prod_axis (2/3 if corners a, b share that coordinate, else 1/3)
+ * (1/27, 1/54, 1/108, 1/216 for corner pairs that differ along 0, 1, 2, 3 axes; sum_ab M8 = 1), m, m' and x_low those of the
+ * self-weight above.
+ *   mass_assemble:    rho0 V_e m(x_e) of the own elements and the ghost layer above, once per design; what the two calls below use
+ *   mass_apply:       y = N M N u on the OWNED node planes (the ghost planes of u are refreshed inside, those of y are left as
+ *                     they are; u != y).  A gather in one fixed order: the same bits on any number of slabs.
+ *   mass_sensitivity: out_e += scale m'(x_e) rho0 V_e sum_l w_l (N V_l)_e^T (M8 (x) I_3) (N V_l)_e   (rho0, x_low of the last
+ *                     mass_assemble; xPhys the design it was called with; w NULL = all 1; ghost planes of every distinct V_l
+ *                     refreshed first).  No reduction, the host does not wait.
+ * For a mode with phi^T B phi = 1:  d lambda / dx = dfdx of tp_elasticity_response(U = V = phi) with the sign turned
+ * (+p x^(p-1) (Emax - Emin) phi_e^T KE phi_e) plus the term with V = phi, scale = -lambda.
+ * TP_ERR_ARG, before the grid is touched, unless e, xPhys, u, y, out and every V[l] are given, rho0 > 0 and finite,
+ * 0 <= x_low < 1, 1 <= ncase <= TP_MAX_CASES and scale is finite; TP_ERR_STATE before the supports are set, and for the last two
+ * before mass_assemble. */
+int tp_elasticity_mass_assemble(tp_elasticity *e, const double *xPhys /*[dev, own elements]*/, double rho0, double x_low);
+int tp_elasticity_mass_apply(tp_elasticity *e, const double *u /*[dev, local nodes*3]*/, double *y /*[dev, local nodes*3]*/);
+int tp_elasticity_mass_sensitivity(tp_elasticity *e, int ncase, const double *const *V /*host array of [dev] pointers*/,
+                            const double *w /*host, NULL = all 1*/, const double *xPhys, double scale,
+                            double *out /*[dev, own elements], added to*/);
 /* introspection for parity tests */
 /* KSPSetTolerances (LinearElasticity.cc:646); a negative value keeps the current one (PETSC_DEFAULT) */
 int tp_elasticity_set_tolerances(tp_elasticity *le, double rtol, double atol, double dtol, int max_it);
@@ -548,6 +569,14 @@ int tp_vec_set(tp_grid *g, double *x, double a, long n);
 int tp_vec_axpby(tp_grid *g, double *y, double a, const double *x, double b, long n);
 int tp_vec_pointwise(tp_grid *g, double *w, const double *x, const double *y, int divide, long n);
 int tp_vec_dot(tp_grid *g, const double *x, const double *y /* NULL: sum of x */, long n, double *out);
+/* Blocks of q <= TP_MAX_CASES vectors (host arrays of q [dev] pointers, n entries each), one pass over the data each.
+ * block_gram: out_qq[i * q + j] (host) = X_i . Y_j over n local entries -- the caller passes OWNED ranges, as for tp_vec_dot --
+ * summed over the ranks of the grid; every vector is read once; deterministic (with X == Y the entries (i, j) and (j, i) are
+ * equal bit for bit, and two calls give the same bits).  block_combine: Z_i = sum_j Q_qq[j * q + i] Y_j over n entries (pass
+ * the whole local arrays: ghost planes included, a combined field needs no refresh); no Z_i may overlap a Y_j or another Z.
+ * TP_ERR_ARG, before the grid is touched, for NULL arguments or vectors, q outside 1..TP_MAX_CASES, n < 1 or an overlap. */
+int tp_vec_block_gram(tp_grid *g, int q, const double *const *X, const double *const *Y, long n, double *out_qq);
+int tp_vec_block_combine(tp_grid *g, int q, const double *const *Y, const double *Q_qq /*host, q*q*/, double *const *Z, long n);
 /* synthetic density of SURVEY.md 8(d), indexed by GLOBAL element id */
 int tp_synth_density(tp_grid *g, double *x, uint64_t seed);
 

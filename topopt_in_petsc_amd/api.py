@@ -18,10 +18,11 @@ from .partition import SlabPartition
 
 
 class TopOptError(RuntimeError):
-    def __init__(self, code, where):
+    def __init__(self, code, where, message=None):
+        """message: the whole text where the code's name alone would not say enough (Eigenmodes: the residuals)"""
         names = {1: "TP_ERR_ARG", 2: "TP_ERR_STATE", 3: "TP_ERR_DIVERGED", 4: "TP_ERR_COMM"}
         msg = names.get(code, "hipError %d" % (code - 1000) if code >= 1000 else str(code))
-        super().__init__("%s failed: %s" % (where, msg))
+        super().__init__(message if message is not None else "%s failed: %s" % (where, msg))
         self.code = code
 
 
@@ -276,6 +277,36 @@ class Grid:
         _chk(self.L.tp_synth_density(self.handle, _ptr(x), seed), "tp_synth_density")
         return x
 
+    # ---- blocks of up to TP_MAX_CASES vectors (the Rayleigh-Ritz step of LinearElasticity.Eigenmodes) ----
+    def BlockGram(self, X, Y):
+        """all len(X)^2 dot products X_i . Y_j over the tensors as they are passed (owned slices: the sum over the ranks is what
+        VecDot gives) in one pass -> numpy array [q, q]"""
+        import numpy as np
+        q = len(X)
+        if len(Y) != q:
+            raise ValueError("BlockGram: %d and %d vectors" % (q, len(Y)))
+        n = X[0].numel() if q else 0
+        assert all(v.numel() == n for v in list(X) + list(Y)), "BlockGram: vectors of different lengths"
+        Xa = (C.c_void_p * max(q, 1))(*[_ptr(v) for v in X])
+        Ya = (C.c_void_p * max(q, 1))(*[_ptr(v) for v in Y])
+        out = (C.c_double * max(q * q, 1))()
+        _chk(self.L.tp_vec_block_gram(self.handle, q, Xa, Ya, n, out), "tp_vec_block_gram")
+        return np.array(out[:q * q]).reshape(q, q)
+
+    def BlockCombine(self, Y, Q, Z):
+        """Z_i = sum_j Q[j, i] Y_j for the q vectors of Y in one pass; no Z_i may overlap a Y_j"""
+        import numpy as np
+        q = len(Y)
+        Q = np.ascontiguousarray(np.asarray(Q, dtype=np.float64))
+        if len(Z) != q or Q.shape != (q, q):
+            raise ValueError("BlockCombine: %d inputs, %d outputs, coefficients of shape %r" % (q, len(Z), Q.shape))
+        n = Y[0].numel() if q else 0
+        assert all(v.numel() == n for v in list(Y) + list(Z)), "BlockCombine: vectors of different lengths"
+        Ya = (C.c_void_p * max(q, 1))(*[_ptr(v) for v in Y])
+        Za = (C.c_void_p * max(q, 1))(*[_ptr(v) for v in Z])
+        _chk(self.L.tp_vec_block_combine(self.handle, q, Ya, Q.ctypes.data_as(C.POINTER(C.c_double)), Za, n), "tp_vec_block_combine")
+        return Z
+
     def sync(self):
         _chk(self.L.tp_sync(self.handle), "tp_sync")
 
@@ -304,6 +335,9 @@ class LinearElasticity:
         self.adjoint_its, self.adjoint_rnorm, self.adjoint_bnorm = 0, 0.0, 0.0
         # self-weight (SetBodyForce): None = off; the total loads F_l + f(xPhys) live in buffers of their own, made on first use
         self.body_force, self.body_xlow, self._case_total = None, 0.1, []
+        # eigenmodes: the block of Ritz vectors persists like the states (warm start across design iterations); made by the
+        # first Eigenmodes call
+        self._eig = None
 
     def close(self):
         if getattr(self, "handle", None):
@@ -412,6 +446,14 @@ class LinearElasticity:
         self.RHS.copy_(RHS)
         _chk(self.L.tp_elasticity_set_bc(self.handle, _ptr(self.N)), "tp_elasticity_set_bc")
 
+    def SetTolerances(self, rtol=-1.0, atol=-1.0, dtol=-1.0, max_it=-1):
+        """KSPSetTolerances; a negative value keeps the current one.  Keeps self.opts in step with the handle (Eigenmodes restores
+        the solver's rtol from there)"""
+        _chk(self.L.tp_elasticity_set_tolerances(self.handle, float(rtol), float(atol), float(dtol), int(max_it)), "tp_elasticity_set_tolerances")
+        for name, v in (("rtol", rtol), ("atol", atol), ("dtol", dtol), ("max_it", max_it)):
+            if v >= 0:
+                setattr(self.opts, name, type(getattr(self.opts, name))(v))
+
     def AssembleStiffnessMatrix(self, xPhys, Emin, Emax, penal):
         _chk(self.L.tp_elasticity_assemble(self.handle, _ptr(xPhys), Emin, Emax, penal), "tp_elasticity_assemble")
 
@@ -473,6 +515,141 @@ class LinearElasticity:
         for rhs, total in zip(self._case_rhs, self._case_total):
             total.copy_(rhs)   # (the ghost planes too)
             self.BodyLoad(xPhys, total, base=total)
+
+    # ---- free vibration: A phi = lambda B phi, A = N K N + (I - N) of the last assembly, B = N M N ----
+    def MassAssemble(self, xPhys, rho0=1.0, x_low=0.1):
+        """rho0 V_e m(xPhys) for MassMult / MassSensitivity, once per design (m: the damped interpolation of SetBodyForce)"""
+        _chk(self.L.tp_elasticity_mass_assemble(self.handle, _ptr(xPhys), float(rho0), float(x_low)), "tp_elasticity_mass_assemble")
+
+    def MassMult(self, u, y=None):
+        """y = N M N u on the owned node planes (ghost planes of y stay as they are)"""
+        y = torch.zeros_like(u) if y is None else y
+        _chk(self.L.tp_elasticity_mass_apply(self.handle, _ptr(u), _ptr(y)), "tp_elasticity_mass_apply")
+        return y
+
+    def MassSensitivity(self, V_list, w, xPhys, scale, out):
+        """out += scale m'(x) rho0 V_e sum_l w_l (N v_l)^T (M8 (x) I3) (N v_l) (w None: all 1); nothing is reduced"""
+        n = len(V_list)
+        Va = (C.c_void_p * max(n, 1))(*[_ptr(v) for v in V_list])
+        wa = None if w is None else (C.c_double * max(n, 1))(*[float(v) for v in w])
+        _chk(self.L.tp_elasticity_mass_sensitivity(self.handle, n, Va, wa, _ptr(xPhys), float(scale), _ptr(out)),
+             "tp_elasticity_mass_sensitivity")
+
+    def _eigen_start(self, q):
+        """q fixed, linearly independent fields of the GLOBAL node index and component (any slab count starts from the same
+        fields), times N: smooth profiles along x in the three directions plus a fixed oscillating part"""
+        p = self.grid.part
+        gn = torch.arange(p.plane * p.nz_local, dtype=torch.float64) + float(p.plane * p.node_z0)
+        xi = (torch.remainder(gn, p.nx) + 1.0) / p.nx
+        out = []
+        for j in range(q):
+            f = torch.zeros(gn.numel(), 3, dtype=torch.float64)
+            f[:, j % 3] = xi ** (1 + j // 3)
+            for c in range(3):
+                f[:, c] += 0.1 * torch.cos(1.7 * (j + 1) * (3.0 * gn + c + 1.0))
+            out.append(f.reshape(-1).to(self.U.device) * self.N)
+        return out
+
+    def Eigenmodes(self, nev, xPhys, rho0=1.0, x_low=0.1, guard=2, tol=1e-6, max_iter=30):
+        """The lowest nev eigenvalues of A phi = lambda B phi on the CURRENT assembly (xPhys: the design it was made from) by
+        subspace iteration with Rayleigh-Ritz on a block of q = nev + guard vectors -> dict(lam, iters, ksp_its, residuals, gap).
+        Every iteration: Y_j = A^-1 B X_j (tp_elasticity_solve from X_j / theta_j), the products A Y and B Y, the two q x q
+        matrices Y^T A Y and Y^T B Y (one pass each), their dense eigenproblem on the host, X = Y Q.  The Ritz values are
+        Rayleigh quotients of true products with A: upper bounds whatever the solve's tolerance.  The products are
+        MatMultKrylov's, the operator CG itself multiplies with: on the lowest modes, which are dominated by translation element
+        by element, it is KE's action to rounding, where MatMult's packed form sits 1e-12 of lambda away (measured).  Stops when
+        ||A x_i - theta_i B x_i|| / ||A x_i|| <= tol for every i < nev; TopOptError at max_iter.  A second call with the same q
+        starts from the previous block (warm start across design iterations).  During the call the solver's rtol is
+        min(opts.rtol, tol / 10); afterwards it is set back to opts.rtol, the value this object holds -- the library has no call
+        that reads the handle's tolerance back, so one set behind this object's back through tp_elasticity_set_tolerances is
+        replaced by it: change the tolerance through SetTolerances, which keeps opts in step.
+        On more than one rank the solver needs at least two multigrid levels: TopOptError (TP_ERR_ARG) otherwise, before anything
+        is launched.  The one run of that configuration (three slabs of two layers, one level) did not finish within four minutes
+        where one rank takes half a second for the same 1435 solver iterations, and why is not known."""
+        import numpy as np
+        import scipy.linalg
+        nev, guard = int(nev), int(guard)
+        q = nev + guard
+        if nev < 1 or guard < 0 or q > _lib.MAX_CASES:
+            raise ValueError("Eigenmodes: need nev >= 1, guard >= 0 and nev + guard <= TP_MAX_CASES = %d, got %d + %d"
+                             % (_lib.MAX_CASES, nev, guard))
+        if self.grid.part.nranks > 1 and self.opts.nlvls < 2:
+            raise TopOptError(1, "Eigenmodes", "Eigenmodes failed: TP_ERR_ARG (on %d ranks the solver needs at least two multigrid "
+                              "levels, it has %d)" % (self.grid.part.nranks, self.opts.nlvls))
+        g, sl = self.grid, self.grid.part.owned_slice(3)
+        self.MassAssemble(xPhys, rho0, x_low)
+        E = self._eig
+        if E is None or E["q"] != q:
+            E = self._eig = dict(q=q, theta=None, X=self._eigen_start(q))
+            for name in ("AX", "BX", "Y", "AY", "BY"):
+                E[name] = [g.node_vec(3) for _ in range(q)]
+        E["nev"], E["lam"] = nev, None
+        X, AX, BX, Y, AY, BY = (E[k] for k in ("X", "AX", "BX", "Y", "AY", "BY"))
+        own = lambda vs: [v[sl] for v in vs]
+        n_all = X[0].numel()
+        ksp_its, res = 0, None
+        _chk(self.L.tp_elasticity_set_tolerances(self.handle, min(self.opts.rtol, 0.1 * tol), -1.0, -1.0, -1), "tp_elasticity_set_tolerances")
+        try:
+            for j in range(q):
+                self.MassMult(X[j], BX[j])
+            for it in range(1, max_iter + 1):
+                for j in range(q):     # Y_j = A^-1 B X_j, from X_j / theta_j
+                    if E["theta"] is None:
+                        Y[j].zero_()
+                    else:
+                        Y[j].copy_(X[j])
+                        _chk(self.L.tp_vec_scale(g.handle, _ptr(Y[j]), 1.0 / E["theta"][j], n_all), "tp_vec_scale")
+                    rc, its, _, _, _ = self._solve(BX[j], Y[j])
+                    _chk(rc, "tp_elasticity_solve (eigenmodes)")
+                    ksp_its += its
+                    # clamped dofs carry exactly 0 (the preconditioner leaves rounding-sized values there)
+                    _chk(self.L.tp_vec_pointwise(g.handle, _ptr(Y[j]), _ptr(Y[j]), _ptr(self.N), 0, n_all), "tp_vec_pointwise")
+                    self.MatMultKrylov(Y[j], AY[j])
+                    self.MassMult(Y[j], BY[j])
+                Kt, Mt = g.BlockGram(own(Y), own(AY)), g.BlockGram(own(Y), own(BY))
+                Kt, Mt = 0.5 * (Kt + Kt.T), 0.5 * (Mt + Mt.T)
+                try:
+                    theta, Q = scipy.linalg.eigh(Kt, Mt)
+                except (np.linalg.LinAlgError, ValueError) as exc:
+                    raise TopOptError(3, "Eigenmodes (Rayleigh-Ritz: the block lost its rank in iteration %d: %s)" % (it, exc))
+                g.BlockCombine(Y, Q, X)
+                g.BlockCombine(AY, Q, AX)
+                g.BlockCombine(BY, Q, BX)
+                E["theta"] = [float(t) for t in theta]
+                for i in range(nev):   # Y is free until the next solve: A x_i - theta_i B x_i
+                    Y[i].copy_(AX[i])
+                    _chk(self.L.tp_vec_axpby(g.handle, _ptr(Y[i]), -E["theta"][i], _ptr(BX[i]), 1.0, n_all), "tp_vec_axpby")
+                rr, aa = g.BlockGram(own(Y[:nev]), own(Y[:nev])), g.BlockGram(own(AX[:nev]), own(AX[:nev]))
+                res = [float(np.sqrt(rr[i, i] / aa[i, i])) for i in range(nev)]
+                if max(res) <= tol:
+                    break
+            else:
+                err = TopOptError(3, "Eigenmodes", "Eigenmodes: %d iterations without reaching tol %.1e; residuals %s, Ritz values %s"
+                                  % (max_iter, tol, " ".join("%.3e" % r for r in res), " ".join("%.9e" % t for t in E["theta"][:nev])))
+                err.residuals = res
+                raise err
+        finally:
+            rc_restore = self.L.tp_elasticity_set_tolerances(self.handle, self.opts.rtol, -1.0, -1.0, -1)
+        _chk(rc_restore, "tp_elasticity_set_tolerances (restoring rtol)")
+        th = E["theta"]
+        E["lam"] = th[:nev]
+        return dict(lam=list(th[:nev]), iters=it, ksp_its=ksp_its, residuals=res,
+                    gap=(th[nev] / th[nev - 1] - 1.0) if guard > 0 else float("inf"))
+
+    def EigenVectors(self):
+        """the nev fields of the last Eigenmodes call, B-normalised (phi_i^T B phi_j = delta_ij); the object's own tensors"""
+        if self._eig is None or self._eig["lam"] is None:
+            raise TopOptError(2, "EigenVectors (no converged Eigenmodes call)")
+        return self._eig["X"][:self._eig["nev"]]
+
+    def EigenSensitivity(self, out, xPhys, Emin, Emax, penal):
+        """out = dJ/dx of J = sum_{i < nev} 1 / lambda_i of the last Eigenmodes call -> J: the bilinear pass of Response with
+        U = V = Phi and the weights lambda_i^-2, plus the mass term with the weights 1 / lambda_i.  Nothing is reduced."""
+        Phi = self.EigenVectors()
+        lam = self._eig["lam"]
+        self.Response(Phi, None, [1.0 / (l * l) for l in lam], xPhys, Emin, Emax, penal, 0.0, dfdx=out, sums=False)
+        self.MassSensitivity(Phi, [1.0 / l for l in lam], xPhys, 1.0, out)
+        return sum(1.0 / l for l in lam)
 
     def KSPSolve(self, hist_cap=0, case=0, rhs=None):
         """solve load case `case` on the last assembly, warm-started from that case's own state (rhs: another right-hand side

@@ -34,12 +34,12 @@ struct BodyFields {
     int ncase;
 };
 
-__device__ __forceinline__ double body_mass(double x, double x_low, double inv_low) {
+__host__ __device__ __forceinline__ double body_mass(double x, double x_low, double inv_low) {
     if (x >= x_low) return x;
     const double t = x * inv_low, t2 = t * t;
     return x * ((t2 * t2 * t) * (6.0 - 5.0 * t));
 }
-__device__ __forceinline__ double body_dmass(double x, double x_low, double inv_low) {
+__host__ __device__ __forceinline__ double body_dmass(double x, double x_low, double inv_low) {
     if (x >= x_low) return 1.0;
     const double t = x * inv_low, t2 = t * t;
     return (t2 * t2 * t) * (36.0 - 35.0 * t);
@@ -95,6 +95,7 @@ __global__ __launch_bounds__(BLK) void k_body_sens(Geom g, BodyPar p, BodyFields
     dfdx[t] += (scale * body_dmass(x[t], p.x_low, p.inv_low)) * acc;
 }
 
+#ifndef TP_BODIES_ONLY  // (tools/mass_bodies_check.cpp takes the kernels and m, m' alone)
 static bool body_par(const double *b3, double x_low, const tp_grid *g, BodyPar *p) {
     if (!(x_low >= 0.0 && x_low < 1.0)) return false;
     for (int c = 0; c < 3; c++)
@@ -154,3 +155,4 @@ extern "C" int tp_elasticity_body_sensitivity(tp_elasticity *e, int ncase, const
     count_launch(g, 24.0 * nel + 24.0 * q.owned_nodes() * (ndistinct + 1), (48.0 * ncase + 2.0 * ncase + 24 + 12) * nel);
     return TP_OK;
 }
+#endif

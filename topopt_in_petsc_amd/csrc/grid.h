@@ -23,6 +23,7 @@ struct tp_grid {
     DevBuf<double> partials;  // [dev] MAX_RED_BLOCKS * 4
     DevBuf<double> scal;      // [dev] 64 device scalars
     DevBuf<unsigned> ticket;  // [dev] arrival counter of the in-kernel reduction tails (common.h: reduce_tail), rests at 0
+    DevBuf<double> gram;      // [dev] tp_vec_block_gram: 64 sums, then 64 x GRAM_BLOCKS block partials (blockvec.h; first use)
     double *h_scal;     // pinned host mirror
     double *h_scal_dev; // its address as the device sees it (kernels that deposit a scalar for the host directly)
     hipEvent_t ev_scal; // marks the read-back of read_scal_begin

@@ -528,6 +528,9 @@ struct tp_elasticity {
     long resp_nb = 0;
     DevBuf<double> d_xg;         // tp_elasticity_body_load: the upper neighbour's first own layer of xPhys (slabs, first use)
     bool have_bc = false, assembled = false;
+    DevBuf<double> d_mc;         // tp_elasticity_mass_assemble: rho0 V_e m(x_e), own + ghost-above layer (first use)
+    double mass_rv = 0.0, mass_xlow = 0.0, mass_invlow = 0.0;   // ... and rho0 V_e, x_low, 1 / x_low of that call
+    bool have_mass = false;
     ~tp_elasticity() {
         sym_slot_release(mg.lv[0].sym_slot);
         if (aux_stream) (void)hipStreamDestroy(aux_stream);
@@ -1383,11 +1386,14 @@ extern "C" int tp_elasticity_last_op_form(const tp_elasticity *e, int *form4) {
 }
 
 // ===========================================================================
-// responses of the state: compliance of one or several load cases, von Mises stress p-norm, self-weight
+// responses of the state: compliance of one or several load cases, von Mises stress p-norm, self-weight, the mass operator and
+// the block-vector passes of the eigen-solver
 // ===========================================================================
 #include "response.h"
 #include "stress.h"
 #include "bodyforce.h"
+#include "mass.h"
+#include "blockvec.h"
 
 // ===========================================================================
 // density / sensitivity filter and Helmholtz PDE filter

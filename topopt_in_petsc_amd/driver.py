@@ -73,7 +73,7 @@ class TopOpt:
     stress_case: int = 0
     # local volume constraint: the p-norm (exponent local_volume_p) of the mean density in a ball of radius local_volume_R
     # around every element held below local_volume as an MMA constraint g = pn / local_volume - 1 behind the stress constraint
-    # (None: none, nothing changes); the constraints are ordered [volume, stress?, local?, solid?, void?]
+    # (None: none, nothing changes); the constraints are ordered [volume, stress?, local?, frequency?, solid?, void?]
     local_volume: float = None
     local_volume_R: float = None
     local_volume_p: float = 16.0
@@ -98,6 +98,16 @@ class TopOpt:
     length_scale_eta: tuple = (0.75, 0.25)
     length_scale_eps: float = 1e-2
     length_scale_start: int = 1
+    # eigenfrequency constraint: the harmonic mean of the lowest frequency_modes eigenvalues of K phi = lambda M phi
+    # (squared angular frequencies; density frequency_rho at x = 1, mass damped below frequency_xlow as for the self-weight) held
+    # above frequency_limit as an MMA constraint g = (frequency_limit / nev) sum 1 / lambda_i - 1 behind the local volume's row,
+    # on xPrint and the assembly of the state solve; the modes are found by subspace iteration to the residual frequency_tol and
+    # warm-started from the previous design iteration (None: none, nothing changes)
+    frequency_limit: float = None
+    frequency_modes: int = 3
+    frequency_rho: float = 1.0
+    frequency_xlow: float = 0.1
+    frequency_tol: float = 1e-6
     history: list = field(default_factory=list)
 
     def __post_init__(self):
@@ -134,6 +144,22 @@ class TopOpt:
                 raise ValueError("local_volume and local_volume_R must be positive")
             self._k_local = 2 if self.stress_limit is not None else 1
             self.m = max(self.m, self._k_local + 1)
+        self._k_freq = None
+        if self.frequency_limit is not None:
+            import math
+            if not (self.frequency_limit > 0.0 and math.isfinite(self.frequency_limit)):
+                raise ValueError("frequency_limit must be positive and finite")
+            if not (self.frequency_rho > 0.0 and math.isfinite(self.frequency_rho)):
+                raise ValueError("frequency_rho must be positive and finite")
+            if not 1 <= int(self.frequency_modes) <= 6:
+                raise ValueError("frequency_modes: 1 to 6 (the block of frequency_modes + 2 vectors holds at most 8)")
+            if not 0.0 <= self.frequency_xlow < 1.0:
+                raise ValueError("frequency_xlow must lie in [0, 1)")
+            if not self.frequency_tol > 0.0:
+                raise ValueError("frequency_tol must be positive")
+            self.frequency_modes = int(self.frequency_modes)
+            self._k_freq = 1 + (self.stress_limit is not None) + (self.local_volume is not None)
+            self.m = max(self.m, self._k_freq + 1)
         nx, ny, nz = self.nxyz
         h = ((self.xc[1] - self.xc[0]) / (nx - 1), (self.xc[3] - self.xc[2]) / (ny - 1),
              (self.xc[5] - self.xc[4]) / (nz - 1))
@@ -236,6 +262,14 @@ class TopOpt:
             g_local, pn_local, rb_max = self.localvol.Constraint(self.xPrint, self.local_volume, self.local_volume_p,
                                                                  dgdx=self.dgdx[self._k_local])
             gxs.append(g_local)
+        if self.frequency_limit is not None:   # on the assembly of the state solve above; the block of modes warm-starts
+            eig = self.physics.Eigenmodes(self.frequency_modes, self.xPrint, self.frequency_rho, self.frequency_xlow,
+                                          tol=self.frequency_tol)
+            row = self.dgdx[self._k_freq]
+            J = self.physics.EigenSensitivity(row, self.xPrint, self.Emin, self.Emax, self.penal)
+            row.mul_(self.frequency_limit / self.frequency_modes)
+            g_freq = self.frequency_limit / self.frequency_modes * J - 1.0
+            gxs.append(g_freq)
         rows = self.dgdx   # what goes back through the overhang filter and the projection: every row but the length scale's
         if self.lengthscale is not None:    # on the blueprint (xTilde, xPhys); d/dxTilde, the projection's derivative inside
             rows, lrows = self.dgdx[:self._k_length[0]], [self.dgdx[k] for k in self._k_length]
@@ -281,6 +315,9 @@ class TopOpt:
             rec["stress_pnorm"], rec["stress_max"], rec["gx_stress"], rec["ksp_its_adjoint"] = pnorm, vm_max, gxs[1], its_adj
         if self.localvol is not None:
             rec["gx_local"], rec["local_pnorm"], rec["local_max"] = g_local, pn_local, rb_max
+        if self.frequency_limit is not None:
+            rec["eig"], rec["gx_frequency"], rec["eig_iters"] = list(eig["lam"]), g_freq, eig["iters"]
+            rec["ksp_its_eigen"], rec["eig_gap"] = eig["ksp_its"], eig["gap"]
         if self.lengthscale is not None:
             rec["gx_solid"], rec["gx_void"] = ls["g_solid"], ls["g_void"]
             rec["length_S_solid"], rec["length_S_void"] = ls["S_solid"], ls["S_void"]

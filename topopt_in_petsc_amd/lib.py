@@ -111,6 +111,9 @@ SYMBOLS = {
     "tp_elasticity_get_stress_form": (_i, [_vp, _vp]),
     "tp_elasticity_body_load": (_i, [_vp, _vp, C.POINTER(_d), _d, _vp, _vp]),
     "tp_elasticity_body_sensitivity": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_d), _vp, C.POINTER(_d), _d, _d, _vp]),
+    "tp_elasticity_mass_assemble": (_i, [_vp, _vp, _d, _d]),
+    "tp_elasticity_mass_apply": (_i, [_vp, _vp, _vp]),
+    "tp_elasticity_mass_sensitivity": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_d), _vp, _d, _vp]),
     "tp_elasticity_petsc_options": (_i, [_vp, C.c_char_p, C.c_size_t]),
     "tp_elasticity_level_count": (_i, [_vp]),
     "tp_elasticity_level_nodes": (_l, [_vp, _i]),
@@ -164,6 +167,8 @@ SYMBOLS = {
     "tp_vec_axpby": (_i, [_vp, _vp, _d, _vp, _d, _l]),
     "tp_vec_pointwise": (_i, [_vp, _vp, _vp, _vp, _i, _l]),
     "tp_vec_dot": (_i, [_vp, _vp, _vp, _l, C.POINTER(_d)]),
+    "tp_vec_block_gram": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp), _l, C.POINTER(_d)]),
+    "tp_vec_block_combine": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_d), C.POINTER(_vp), _l]),
     "tp_elasticity_set_tolerances": (_i, [_vp, _d, _d, _d, _i]),
     "tp_filter_mult_h": (_i, [_vp, _vp, _vp]),
     "tp_mma_restart_get": (_i, [_vp, _vp, _vp, _vp, _vp]),
