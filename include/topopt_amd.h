@@ -523,6 +523,30 @@ int tp_overhang_forward(tp_overhang *ov, const double *x, double *xi);   /* TP_E
 int tp_overhang_adjoint(tp_overhang *ov, int nvec, double *const *g);
 int tp_overhang_last_chunk(const tp_overhang *ov);              /* layers per launch of the last sweep */
 
+/* ---- passive regions: elements held at a fixed density (no reference counterpart) ---- */
+/* Labels per own element, natural order: 0 active, 1 void, 2 solid.  The optimiser works on the active elements alone, packed in
+ * ascending element order (n_active entries); the filter and the physics work on the full fields (all own elements) with the
+ * passive values imposed.  The labels come from the host once; create builds the int32 index list of the active elements there
+ * and uploads both.  TP_ERR_ARG for a label above 2.
+ * The four per-iteration calls take host arrays of nvec [dev] pointers, 1 <= nvec <= TP_PASSIVE_MAXVEC (the objective row, the 7
+ * constraint rows MMA allows, the design and spare), and handle all of them in ONE launch:
+ *   impose   passive entries of every x[v] <- v_void / v_solid by label; active entries are not written
+ *   zero     passive entries of every rows[v] <- +0.0 whatever they held (NaN included); active entries are not written
+ *   gather   packed[v][a] = full[v][idx[a]], a < n_active
+ *   scatter  full[v][idx[a]] = packed[v][a]; passive entries of full are not written
+ * TP_ERR_ARG, before the handle is used, for a NULL handle, array or vector, nvec outside 1..TP_PASSIVE_MAXVEC, and for
+ * full[v] == packed[w] with any v, w.  Without active elements gather and scatter, without passive ones impose and zero, return
+ * TP_OK and launch nothing. */
+#define TP_PASSIVE_MAXVEC 12
+typedef struct tp_passive tp_passive;
+int tp_passive_create(tp_passive **p, tp_grid *g, const unsigned char *label_host /* own elements, natural order */);
+int tp_passive_destroy(tp_passive *p);                          /* NULL: TP_OK */
+int tp_passive_counts(const tp_passive *p, long *n_active, long *n_void, long *n_solid);   /* own elements; each may be NULL */
+int tp_passive_impose(tp_passive *p, int nvec, double *const *x, double v_void, double v_solid);
+int tp_passive_zero(tp_passive *p, int nvec, double *const *rows);
+int tp_passive_gather(tp_passive *p, int nvec, const double *const *full, double *const *packed);
+int tp_passive_scatter(tp_passive *p, int nvec, const double *const *packed, double *const *full);
+
 /* ---- MMA optimizer step on the device (MMA.cc) ------------ */
 typedef struct tp_mma tp_mma;
 /* MMA::MMA(n, m, x) (MMA.cc:108-190): a = 0, c = 1000, d = 0, asymptote factors 0.5 / 0.7 / 1.2.

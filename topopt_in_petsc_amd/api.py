@@ -1130,6 +1130,139 @@ class LengthScale:
         return ts, tv
 
 
+def passive_labels(nxyz, xc, shapes):
+    """Global label array (numpy uint8, natural order: x fastest, then y, then z; 0 active, 1 void, 2 solid) of a box of
+    nxyz NODES spanning xc = (x0, x1, y0, y1, z0, z1) from a list of shapes in physical coordinates:
+        ("solid" | "void", "box", (x0, x1, y0, y1, z0, z1))
+        (kind, "sphere", (cx, cy, cz, r))
+        (kind, "cylinder", (axis, c1, c2, r))     axis 0 / 1 / 2 or "x" / "y" / "z"; infinite along it, (c1, c2) the centre in
+                                                  the two other coordinates in ascending axis order
+    An element belongs to a shape when its centre xc0_a + (i_a + 0.5) h_a lies inside or on the boundary; later shapes override
+    earlier ones.  Host-side set-up, runs once."""
+    import numpy as np
+    ne = [int(n) - 1 for n in nxyz]
+    if len(ne) != 3 or min(ne) < 1 or len(xc) != 6:
+        raise ValueError("passive_labels: need three node counts >= 2 and xc = (x0, x1, y0, y1, z0, z1)")
+    c = []
+    for a in range(3):
+        lo, hi = float(xc[2 * a]), float(xc[2 * a + 1])
+        c.append(lo + (np.arange(ne[a]) + 0.5) * ((hi - lo) / ne[a]))
+    Z, Y, X = np.meshgrid(c[2], c[1], c[0], indexing="ij")
+    P = (X, Y, Z)
+    lab = np.zeros((ne[2], ne[1], ne[0]), dtype=np.uint8)
+    for shape in shapes:
+        try:
+            kind, form, num = shape
+            num = tuple(num)
+        except (TypeError, ValueError):
+            raise ValueError("passive_labels: a shape is (kind, form, numbers), got %r" % (shape,))
+        if kind not in ("void", "solid"):
+            raise ValueError("passive_labels: kind must be 'solid' or 'void', got %r" % (kind,))
+        if form == "box" and len(num) == 6:
+            b = [float(v) for v in num]
+            inside = np.ones(lab.shape, dtype=bool)
+            for a in range(3):
+                inside &= (P[a] >= b[2 * a]) & (P[a] <= b[2 * a + 1])
+        elif form == "sphere" and len(num) == 4:
+            cx, cy, cz, r = (float(v) for v in num)
+            inside = (X - cx) ** 2 + (Y - cy) ** 2 + (Z - cz) ** 2 <= r * r
+        elif form == "cylinder" and len(num) == 4:
+            axis = {"x": 0, "y": 1, "z": 2}.get(num[0], num[0])
+            if axis not in (0, 1, 2):
+                raise ValueError("passive_labels: cylinder axis must be 0, 1, 2 or 'x', 'y', 'z', got %r" % (num[0],))
+            u, v = [P[a] for a in range(3) if a != axis]
+            c1, c2, r = (float(t) for t in num[1:])
+            inside = (u - c1) ** 2 + (v - c2) ** 2 <= r * r
+        else:
+            raise ValueError("passive_labels: box (6 numbers), sphere (4) or cylinder (axis and 3), got %r" % (shape,))
+        lab[inside] = 1 if kind == "void" else 2
+    return lab.reshape(-1)
+
+
+class Passive:
+    """Passive regions (tp_passive): labels per own element (0 active, 1 void, 2 solid) and the four kernels between the full
+    fields the filter and the physics see and the packed vectors of the active elements the optimiser sees.  Every call takes a
+    list of 1 to MAXVEC tensors and handles all of them in one launch."""
+    MAXVEC = _lib.PASSIVE_MAXVEC
+
+    def __init__(self, grid, labels_own):
+        import numpy as np
+        self.grid, self.L = grid, grid.L
+        lab = np.ascontiguousarray(np.asarray(labels_own), dtype=np.uint8)
+        if lab.ndim != 1 or lab.size != grid.n_own_elems:
+            raise ValueError("Passive: need %d labels (own elements), got an array of shape %r" % (grid.n_own_elems, lab.shape))
+        self.handle = C.c_void_p()
+        _chk(self.L.tp_passive_create(C.byref(self.handle), grid.handle, lab.ctypes.data), "tp_passive_create")
+        grid._adopt(self)
+        self.n_active, self.n_void, self.n_solid = self.counts()
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.L.tp_passive_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def counts(self):
+        """(n_active, n_void, n_solid) of the own elements"""
+        a, v, s = C.c_long(), C.c_long(), C.c_long()
+        _chk(self.L.tp_passive_counts(self.handle, C.byref(a), C.byref(v), C.byref(s)), "tp_passive_counts")
+        return a.value, v.value, s.value
+
+    def packed_vec(self, value=0.0):
+        return torch.full((self.n_active,), value, dtype=torch.float64, device=self.grid.device)
+
+    def _arr(self, vecs, numel):
+        for t in vecs:
+            assert t.numel() == numel, "Passive: a vector of %d entries where %d are needed" % (t.numel(), numel)
+        return (C.c_void_p * max(len(vecs), 1))(*[_ptr(t) for t in vecs])
+
+    def _nothing_active(self, full, packed):
+        """no active element: the packed tensors are empty and have no address to hand to the library, which would launch
+        nothing for them; the count and the lengths are checked as the library and _arr check them"""
+        if self.n_active:
+            return False
+        if not 1 <= len(full) <= self.MAXVEC:
+            raise TopOptError(1, "tp_passive_gather / tp_passive_scatter")
+        assert all(t.numel() == 0 for t in packed) and all(t.numel() == self.grid.n_own_elems for t in full)
+        return True
+
+    def Impose(self, vecs, v_void, v_solid):
+        """passive entries of every full tensor of the list <- v_void / v_solid by label; active entries stay"""
+        _chk(self.L.tp_passive_impose(self.handle, len(vecs), self._arr(vecs, self.grid.n_own_elems), float(v_void), float(v_solid)),
+             "tp_passive_impose")
+        return vecs
+
+    def Zero(self, rows):
+        """passive entries of every full tensor of the list <- +0.0; active entries stay"""
+        _chk(self.L.tp_passive_zero(self.handle, len(rows), self._arr(rows, self.grid.n_own_elems)), "tp_passive_zero")
+        return rows
+
+    def Gather(self, full, packed):
+        """packed[v] <- the active entries of full[v], ascending element order"""
+        if len(full) != len(packed):
+            raise ValueError("Passive.Gather: %d full and %d packed vectors" % (len(full), len(packed)))
+        if self._nothing_active(full, packed):
+            return packed
+        _chk(self.L.tp_passive_gather(self.handle, len(full), self._arr(full, self.grid.n_own_elems),
+                                      self._arr(packed, self.n_active)), "tp_passive_gather")
+        return packed
+
+    def Scatter(self, packed, full):
+        """the active entries of full[v] <- packed[v]; passive entries stay"""
+        if len(full) != len(packed):
+            raise ValueError("Passive.Scatter: %d packed and %d full vectors" % (len(packed), len(full)))
+        if self._nothing_active(full, packed):
+            return full
+        _chk(self.L.tp_passive_scatter(self.handle, len(full), self._arr(packed, self.n_active),
+                                       self._arr(full, self.grid.n_own_elems)), "tp_passive_scatter")
+        return full
+
+
 class Overhang:
     """Overhang (self-support) filter (tp_overhang): the printed density of a part built layer by layer along `build`
     ("+z", "-z", "+y", "-y"; the baseplate lies at the low end for +), and the transpose of its Jacobian."""

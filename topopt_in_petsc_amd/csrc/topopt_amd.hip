@@ -1416,6 +1416,11 @@ extern "C" int tp_elasticity_last_op_form(const tp_elasticity *e, int *form4) {
 #include "overhang.h"
 
 // ===========================================================================
+// passive regions: fixed solid / void elements beside the packed design
+// ===========================================================================
+#include "passive.h"
+
+// ===========================================================================
 // optimizer step around the path (MMA), SURVEY.md 8(f)-1
 // ===========================================================================
 #include "mma.h"

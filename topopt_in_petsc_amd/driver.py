@@ -16,7 +16,7 @@ import torch
 from . import mpiio
 import ctypes as C
 
-from .api import Filter, Grid, LengthScale, LinearElasticity, LocalVolume, MMA, Overhang, SolverOptions, _chk, _ptr, check_body_force
+from .api import Filter, Grid, LengthScale, LinearElasticity, LocalVolume, MMA, Overhang, Passive, SolverOptions, _chk, _ptr, check_body_force, passive_labels
 
 
 @dataclass
@@ -108,6 +108,10 @@ class TopOpt:
     frequency_rho: float = 1.0
     frequency_xlow: float = 0.1
     frequency_tol: float = 1e-6
+    # passive regions: the global label array (natural order; 0 active, 1 void, 2 solid) or a list of shapes for
+    # api.passive_labels.  Void elements are held at x = Xmin, xPhys = 0, solid ones at x = Xmax, xPhys = 1; MMA works on the
+    # active elements alone, packed; the volume constraint stays the mean over ALL elements (None: none, nothing changes)
+    passive: object = None
     history: list = field(default_factory=list)
 
     def __post_init__(self):
@@ -170,6 +174,7 @@ class TopOpt:
             self.m += nk
             if self.length_scale_c is None:
                 self.length_scale_c = self.rmin ** 4 / min(h) ** 2
+        labels = self._check_passive() if self.passive is not None else None
         self.grid = Grid(nx, ny, nz, h, rank=self.rank, nranks=self.nranks)
         so = self.solver or SolverOptions(nlvls=self.nlvls, nu=self.nu)
         self.physics = LinearElasticity(self.grid, so)
@@ -196,11 +201,24 @@ class TopOpt:
         self.xTilde, self.xPhys = g.elem_vec(self.volfrac), g.elem_vec(self.volfrac)
         self.xPrint = g.elem_vec(self.volfrac) if self.overhang_filter is not None else self.xPhys
         self.dfdx, self.dgdx = g.elem_vec(), [g.elem_vec() for _ in range(self.m)]
-        self.xmin, self.xmax, self.xold = g.elem_vec(), g.elem_vec(), g.elem_vec(self.volfrac)
+        # what MMA works on: the fields themselves, or with passive regions the packed vectors of the active elements
+        self.regions, n_mma = None, None
+        self._xd, self._dfd, self._dgd = self.x, self.dfdx, self.dgdx
+        new = g.elem_vec
+        if labels is not None:
+            n_own = g.part.n_own_elems
+            self.labels_own = labels[self.rank * n_own:(self.rank + 1) * n_own]
+            self.regions = pr = Passive(g, self.labels_own)
+            self.x.fill_(self._x0)
+            pr.Impose([self.x], self.Xmin, self.Xmax)   # once: the filter sees the fixed neighbours
+            new, n_mma = pr.packed_vec, self.n_active
+            self.xa = self._xd = new(self._x0)
+            self._dfd, self._dgd = new(), [new() for _ in range(self.m)]
+        self.xmin, self.xmax, self.xold = new(), new(), new(self.volfrac if labels is None else self._x0)
         if self.aMMA is None and self.cMMA is None and self.dMMA is None:
-            self.mma = MMA(g, self.x, self.m)
+            self.mma = MMA(g, self._xd, self.m, n_global=n_mma)
         else:
-            self.mma = MMA(g, self.x, self.m, a=0.0 if self.aMMA is None else self.aMMA,
+            self.mma = MMA(g, self._xd, self.m, n_global=n_mma, a=0.0 if self.aMMA is None else self.aMMA,
                            c=1000.0 if self.cMMA is None else self.cMMA, d=0.0 if self.dMMA is None else self.dMMA)
         if self.mma_asymptotes is not None:
             self.mma.SetAsymptotes(*self.mma_asymptotes)
@@ -221,7 +239,47 @@ class TopOpt:
                 and os.path.exists(self.restartFileItr):
             self.ReadRestartFiles(self.restartFileVec, self.restartFileItr, self.restartFileVecSol)
         # main.cc:48
+        self._filter_project()
+
+    def _check_passive(self):
+        """the global label array of `passive`, checked; sets n_active (global) and the active elements' start value _x0.
+        Everything here is host arithmetic on the global labels: it comes before any device object and needs no communication"""
+        nx, ny, nz = self.nxyz
+        n = (nx - 1) * (ny - 1) * (nz - 1)
+        p = self.passive
+        if isinstance(p, (list, tuple)) and (len(p) == 0 or isinstance(p[0], (list, tuple))):
+            p = passive_labels(self.nxyz, self.xc, p)
+        lab = np.asarray(p)
+        if lab.ndim != 1 or lab.size != n:
+            raise ValueError("passive: need %d labels (all elements, natural order), got an array of shape %r" % (n, lab.shape))
+        if lab.size and (lab.min() < 0 or lab.max() > 2):
+            raise ValueError("passive: labels are 0 (active), 1 (void) or 2 (solid)")
+        lab = np.ascontiguousarray(lab, dtype=np.uint8)
+        if self.length_scale is not None:
+            raise ValueError("length_scale together with passive regions is not supported: its constraints differentiate xPhys "
+                             "with respect to xTilde on every element")
+        n_active, n_solid = int((lab == 0).sum()), int((lab == 2).sum())
+        if n_active == 0:
+            raise ValueError("passive: no active element is left")
+        if (nz - 1) % self.nranks == 0:   # (otherwise the grid refuses the slabs)
+            per = lab.reshape(self.nranks, -1)
+            empty = [r for r in range(self.nranks) if per[r].all()]
+            if empty:
+                raise ValueError("passive: the slab of rank %s has no active element" % ", ".join(str(r) for r in empty))
+        if n_solid / n >= self.volfrac:
+            raise ValueError("passive: the solid elements alone fill %.4f of the volume, volfrac is %.4f" % (n_solid / n, self.volfrac))
+        # the volume constraint starts at equality, as in the reference; without passive elements this is volfrac itself
+        self._x0 = self.volfrac if n_active == n else (self.volfrac * n - n_solid) / n_active
+        if not self.Xmin <= self._x0 <= self.Xmax:
+            raise ValueError("passive: the active elements would start at %.4f, outside [Xmin, Xmax] = [%g, %g]" % (self._x0, self.Xmin, self.Xmax))
+        self.n_active = n_active
+        return lab
+
+    def _filter_project(self):
+        """x -> xTilde -> xPhys (main.cc:48, :98), the passive values imposed on xPhys (xTilde stays as filtered), then xPrint"""
         self.filt.FilterProject(self.x, self.xTilde, self.xPhys, self.projectionFilter, self.beta, self.eta)
+        if self.regions is not None:
+            self.regions.Impose([self.xPhys], 0.0, 1.0)
         self._print()
 
     def _body_share(self):
@@ -287,18 +345,23 @@ class TopOpt:
                 gxs.extend(g_length)
         if self.overhang_filter is not None:   # d/dxPrint -> d/dxPhys, all of them in one sweep
             self.overhang_filter.Adjoint([self.dfdx] + rows)
+        if self.regions is not None:   # the rows are d/dxPhys now, and xPhys does not move on passive elements
+            self.regions.Zero([self.dfdx] + rows)
         self.filt.Gradients(self.x, self.xTilde, self.dfdx, rows, self.projectionFilter, self.beta, self.eta)
         if self.lengthscale is not None:
             self.filt.GradientsFromTilde(self.x, lrows)
-        self.mma.SetOuterMovelimit(self.Xmin, self.Xmax, self.movlim, self.x, self.xmin, self.xmax)  # :81
-        self.mma.Update(self.x, self.dfdx, gxs, self.dgdx, self.xmin, self.xmax)                 # :85
+        if self.regions is not None:   # the active entries of the objective's row and every constraint's, one launch
+            self.regions.Gather([self.dfdx] + self.dgdx, [self._dfd] + self._dgd)
+        self.mma.SetOuterMovelimit(self.Xmin, self.Xmax, self.movlim, self._xd, self.xmin, self.xmax)  # :81
+        self.mma.Update(self._xd, self._dfd, gxs, self._dgd, self.xmin, self.xmax)               # :85
+        if self.regions is not None:
+            self.regions.Scatter([self.xa], [self.x])
         if self.kkt:
-            kkt = self.mma.KKTresidual(self.x, self.dfdx, gxs, self.dgdx, self.xmin, self.xmax)
-        ch = self.mma.DesignChange(self.x, self.xold)                                            # :89
+            kkt = self.mma.KKTresidual(self._xd, self._dfd, gxs, self._dgd, self.xmin, self.xmax)
+        ch = self.mma.DesignChange(self._xd, self.xold)                                          # :89
         if self.projectionFilter:                                                                # :93-95
             self._increase_beta(gx, ch)
-        self.filt.FilterProject(self.x, self.xTilde, self.xPhys, self.projectionFilter, self.beta, self.eta)  # :98
-        self._print()
+        self._filter_project()                                                                   # :98
         mnd = self.filt.GetMND(self.xPrint)                                                      # :102
         torch.cuda.synchronize()
         t2 = time.perf_counter()
@@ -325,6 +388,8 @@ class TopOpt:
             rec["print_loss"] = self._mean(self.xPhys - self.xPrint)
         if self.body_force is not None:
             rec["body_share"] = body_share
+        if self.regions is not None:
+            rec["n_active"] = self.n_active
         self.history.append(rec)
         if verbose and self.rank == 0:
             print("It.: %i, True fx: %f, Scaled fx: %f, gx[0]: %f, ch.: %f, mnd.: %f, time: %f"
@@ -363,7 +428,12 @@ class TopOpt:
         tag = "01" if self._flip else "00"
         g = self.grid
         xo1, xo2, U, L = g.elem_vec(), g.elem_vec(), g.elem_vec(), g.elem_vec()
-        self.mma.Restart(xo1, xo2, U, L)
+        if self.regions is None:
+            self.mma.Restart(xo1, xo2, U, L)
+        else:   # the files keep their full-length layout: MMA's packed vectors into zero-filled full ones
+            packed = [self.regions.packed_vec() for _ in range(4)]
+            self.mma.Restart(*packed)
+            self.regions.Scatter(packed, [xo1, xo2, U, L])
         vecs = [self._gather(v) for v in (self.x, self.xPhys, xo1, xo2, U, L)]
         # the further cases' states follow the first Vec (the reference's reader takes the first one only)
         sols = [self._gather(self.physics.LoadCaseU(c)[self.grid.part.owned_slice(3)]) for c in range(self.physics.ncases)]
@@ -381,8 +451,13 @@ class TopOpt:
         self.xPhys.copy_(self._own(xPhys))
         self.fscale = float(fscale)
         self.itr = int(itr)
+        if self.regions is not None:   # the files are full length: the design on the active elements ...
+            self.regions.Gather([self.x], [self.xa])
         if not self.onlyLoadDesign:
-            self.mma.SetRestart(self.itr, self._own(xo1), self._own(xo2), self._own(U), self._own(L))
+            state = [self._own(xo1), self._own(xo2), self._own(U), self._own(L)]
+            if self.regions is not None:   # ... and MMA's vectors
+                state = self.regions.Gather(state, [self.regions.packed_vec() for _ in range(4)])
+            self.mma.SetRestart(self.itr, *state)
         if solfile and os.path.exists(solfile):
             sols = mpiio.read_petsc_vecs(solfile)   # a file with fewer states than cases leaves the others at zero
             sl = self.grid.part.owned_slice(3)

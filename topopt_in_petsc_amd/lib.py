@@ -199,11 +199,19 @@ SYMBOLS = {
     "tp_lengthscale_constraints": (_i, [_vp, _vp, _vp, _i, _d, _d, _d, _d, _d, _d, _i, C.POINTER(_d), C.POINTER(_d), _vp, _vp]),
     "tp_lengthscale_get_terms": (_i, [_vp, _vp, _vp]),
     "tp_filter_gradients_from_tilde": (_i, [_vp, _vp, _i, C.POINTER(_vp)]),
+    "tp_passive_create": (_i, [C.POINTER(_vp), _vp, _vp]),
+    "tp_passive_destroy": (_i, [_vp]),
+    "tp_passive_counts": (_i, [_vp, C.POINTER(_l), C.POINTER(_l), C.POINTER(_l)]),
+    "tp_passive_impose": (_i, [_vp, _i, C.POINTER(_vp), _d, _d]),
+    "tp_passive_zero": (_i, [_vp, _i, C.POINTER(_vp)]),
+    "tp_passive_gather": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp)]),
+    "tp_passive_scatter": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp)]),
 }
 
 
 ABI_VERSION = 4   # TP_ABI_VERSION of include/topopt_amd.h
 MAX_CASES = 8     # TP_MAX_CASES: load cases of one tp_elasticity_response call
+PASSIVE_MAXVEC = 12   # TP_PASSIVE_MAXVEC: vectors of one tp_passive_impose / zero / gather / scatter call
 
 
 def load_library():
