@@ -547,6 +547,25 @@ int tp_passive_zero(tp_passive *p, int nvec, double *const *rows);
 int tp_passive_gather(tp_passive *p, int nvec, const double *const *full, double *const *packed);
 int tp_passive_scatter(tp_passive *p, int nvec, const double *const *packed, double *const *full);
 
+/* ---- robust design: eroded / nominal / dilated projections of one filtered field (no reference counterpart) ---- */
+/* project  out[k][i] = H(xTilde[i]; beta, eta[k]) for k < nproj in ONE launch that reads xTilde once; each field has the bits of
+ *          tp_filter_project's projection at its threshold.  With p a void element receives 0.0 and a solid one 1.0 in every field
+ *          (the projection followed by tp_passive_impose(.., 0, 1)).  With sums the nproj sums of the values as stored, over all
+ *          ranks, are returned to the host (one read, blocking); without, nothing is reduced and the host does not wait.
+ * chain    rows[r][i] *= dH/dxTilde(xTilde[i]; beta, eta_row[r]), tp_filter_gradients' projection factor; the factor is evaluated
+ *          once per distinct threshold -- at most TP_ROBUST_MAXPROJ of them -- and element.  With p the passive entries of every
+ *          row are stored as +0.0 whatever they held (the chain followed by tp_passive_zero).
+ * TP_ERR_ARG, before the grid is used, for a NULL grid, field, array or vector, nproj outside 1..TP_ROBUST_MAXPROJ, nrows outside
+ * 1..TP_ROBUST_MAXROWS, more than TP_ROBUST_MAXPROJ distinct eta_row, beta <= 0 or not finite, a threshold outside [0, 1], an
+ * out[k] / rows[r] equal to xTilde or to another one, and a p of another grid. */
+#define TP_ROBUST_MAXPROJ 3
+#define TP_ROBUST_MAXROWS 8
+int tp_robust_project(tp_grid *g, const double *xTilde, double beta, int nproj, const double *eta /* [nproj], host */,
+                      double *const *out /* [nproj] dev, own elements */, const tp_passive *p /* or NULL */,
+                      double *sums /* [nproj] host, or NULL */);
+int tp_robust_chain(tp_grid *g, const double *xTilde, double beta, int nrows, double *const *rows /* dev */,
+                    const double *eta_row /* [nrows], host */, const tp_passive *p /* or NULL */);
+
 /* ---- MMA optimizer step on the device (MMA.cc) ------------ */
 typedef struct tp_mma tp_mma;
 /* MMA::MMA(n, m, x) (MMA.cc:108-190): a = 0, c = 1000, d = 0, asymptote factors 0.5 / 0.7 / 1.2.

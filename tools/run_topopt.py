@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """End-to-end run of the reference's optimisation loop on the MI355X path.
-usage: run_topopt.py [--loadcase top[:weight]]... [--stress-limit L [--stress-p P] [--stress-q q]] [--local-volume ALPHA:R] [--overhang +z|-z|+y|-y] [--self-weight bx,by,bz[:xlow] [--no-point-load]] [--length-scale both|solid|void[:C]] [--frequency-limit L[:nev]] [--passive solid|void:box|sphere|cylinder:numbers]... ex ey ez nlvls n_iter [filter [nsmooth ncoarse]]
+usage: run_topopt.py [--loadcase top[:weight]]... [--stress-limit L [--stress-p P] [--stress-q q]] [--local-volume ALPHA:R] [--overhang +z|-z|+y|-y] [--self-weight bx,by,bz[:xlow] [--no-point-load]] [--length-scale both|solid|void[:C]] [--frequency-limit L[:nev]] [--passive solid|void:box|sphere|cylinder:numbers]... [--robust ETA_E,ETA_N,ETA_D[:every]] ex ey ez nlvls n_iter [filter [nsmooth ncoarse]]
 (e.g. 128 128 128 5 20 1 2 45: the cycle of bench.py; --loadcase top:0.5 adds the line load on the upper edge as a second load
 case of weight 0.5 -- the objective becomes the weighted sum of the cases' compliances; --stress-limit L holds the von Mises
 p-norm of load case 0 below L as a second constraint, exponent --stress-p (8), stress relaxation x^q with --stress-q (0.5); --local-volume ALPHA:R holds the mean density in a ball of
@@ -14,7 +14,9 @@ DESIGN 4.13 as the last constraints, decay C in length^2 (default rmin^4 / h^2),
 --passive KIND:SHAPE:numbers holds the elements whose centres lie in a shape at full density (solid) or empty (void), the passive
 regions of DESIGN 4.15, in physical coordinates (the box is ex/ey x 1 x ez/ey): box:x0,x1,y0,y1,z0,z1, sphere:cx,cy,cz,r or
 cylinder:axis,c1,c2,r (axis x, y or z, infinite along it); later shapes override earlier ones, e.g.
---passive solid:box:1.9,2,0,1,0,0.1 --passive void:sphere:1,0.5,0.5,0.25)"""
+--passive solid:box:1.9,2,0,1,0,0.1 --passive void:sphere:1,0.5,0.5,0.25; --robust 0.7,0.5,0.3[:every] runs the robust formulation of
+DESIGN 4.16 with the Heaviside projection switched on: the compliance of the design eroded at 0.7, the volume held on the design
+dilated at 0.3 so that the nominal one at 0.5 meets volfrac, the dilated target recomputed every `every` (20) iterations)"""
 import os
 import sys
 
@@ -99,11 +101,18 @@ for v in _option("--passive", ": solid|void:box|sphere|cylinder:numbers"):
         shapes.append((kind, form, tuple([a if a in ("x", "y", "z") else int(a) for a in axis] + [float(t) for t in nums])))
     except ValueError:
         sys.exit("--passive needs KIND:SHAPE:numbers, e.g. solid:box:1.9,2,0,1,0,0.1, got %r" % v)
+robust_arg, robust = _last("--robust"), {}
+if robust_arg is not None:
+    etas, _, every = robust_arg.partition(":")
+    try:
+        robust = dict(robust=tuple(float(v) for v in etas.split(",")), robust_volume_every=int(every) if every else 20, projectionFilter=True)
+    except ValueError:
+        sys.exit("--robust needs ETA_E,ETA_N,ETA_D[:every], e.g. 0.7,0.5,0.3:20, got %r" % robust_arg)
 ex, ey, ez, nlv, nit = [int(v) for v in sys.argv[1:6]]
 flt = int(sys.argv[6]) if len(sys.argv) > 6 else 1
 h = 1.0 / ey
 opt = tp.TopOpt(nxyz=(ex + 1, ey + 1, ez + 1), xc=(0, ex * h, 0, 1, 0, ez * h), nlvls=nlv, rmin=2.56 * h, filter=flt,
-                loadcases=loadcases or None, **stress, **local, overhang=overhang, **body, **length, **frequency, passive=shapes or None,
+                loadcases=loadcases or None, **stress, **local, overhang=overhang, **body, **length, **frequency, passive=shapes or None, **robust,
                 solver=tp.SolverOptions(nlvls=nlv, **(dict(nsmooth=int(sys.argv[7]), ncoarse=int(sys.argv[8])) if len(sys.argv) > 8 else {})))
 print("# %dx%dx%d elements, %d DOF, %d MG levels, filter %d, rmin %.4f" % (ex, ey, ez, 3 * (ex + 1) * (ey + 1) * (ez + 1), nlv, flt, 2.56 * h))
 for it in range(nit):
@@ -130,5 +139,8 @@ for it in range(nit):
         xp = opt.xPhys.cpu().numpy()
         print("Passive:       %d active of %d elements | xPhys exact on the own void elements: %s, solid: %s"
               % (r["n_active"], ex * ey * ez, bool((xp[lab == 1] == 0.0).all()), bool((xp[lab == 2] == 1.0).all())), flush=True)
+    if "vol_real" in r:
+        print("Robust:        eta: %s, beta: %g | volume eroded / nominal / dilated: %s, dilated target: %f"
+              % (",".join("%g" % v for v in opt.robust), opt.beta, " ".join("%f" % v for v in r["vol_real"]), r["vol_dilated_target"]), flush=True)
     if "gx_local" in r:
         print("Local volume:  p-norm: %f, max: %f, gx[%d]: %f" % (r["local_pnorm"], r["local_max"], opt.m - 1, r["gx_local"]), flush=True)

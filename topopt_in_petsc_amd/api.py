@@ -1263,6 +1263,48 @@ class Passive:
         return full
 
 
+class Robust:
+    """Robust three-field formulation (tp_robust_project / tp_robust_chain): one filtered field projected at up to MAXPROJ
+    thresholds with one beta in one launch -- the eroded, nominal and dilated designs -- and the projections' derivatives put on
+    up to MAXROWS gradient rows in one launch.  Holds no device object of its own."""
+    MAXPROJ, MAXROWS = _lib.ROBUST_MAXPROJ, _lib.ROBUST_MAXROWS
+
+    def __init__(self, grid):
+        self.grid, self.L = grid, grid.L
+
+    def _vecs(self, vecs):
+        n = self.grid.n_own_elems
+        for t in vecs:
+            assert t.numel() == n, "Robust: a vector of %d entries where %d are needed" % (t.numel(), n)
+        return (C.c_void_p * max(len(vecs), 1))(*[_ptr(t) for t in vecs])
+
+    def Project(self, xTilde, beta, etas, outs, passive=None, sums=True):
+        """outs[k] <- H(xTilde; beta, etas[k]), the bits of Filter.FilterProject's projection at that threshold; with a Passive
+        the void elements receive 0.0 and the solid ones 1.0 in every field.  sums=True: -> the list of the fields' sums as
+        stored, over all ranks (the host waits); sums=False: -> None, nothing is reduced"""
+        if len(etas) != len(outs):
+            raise ValueError("Robust.Project: %d thresholds and %d fields" % (len(etas), len(outs)))
+        assert xTilde.numel() == self.grid.n_own_elems
+        k = len(outs)
+        eta = (C.c_double * max(k, 1))(*[float(e) for e in etas])
+        s = (C.c_double * max(k, 1))() if sums else None
+        _chk(self.L.tp_robust_project(self.grid.handle, _ptr(xTilde), float(beta), k, eta, self._vecs(outs),
+                                      passive.handle if passive is not None else None, s), "tp_robust_project")
+        return [s[i] for i in range(k)] if sums else None
+
+    def Chain(self, xTilde, beta, rows, etas_of_rows, passive=None):
+        """rows[r] *= dH/dxTilde(xTilde; beta, etas_of_rows[r]) in place, Filter.Gradients' projection factor; at most MAXPROJ
+        distinct thresholds.  With a Passive the passive entries of every row become +0.0"""
+        if len(etas_of_rows) != len(rows):
+            raise ValueError("Robust.Chain: %d thresholds and %d rows" % (len(etas_of_rows), len(rows)))
+        assert xTilde.numel() == self.grid.n_own_elems
+        k = len(rows)
+        eta = (C.c_double * max(k, 1))(*[float(e) for e in etas_of_rows])
+        _chk(self.L.tp_robust_chain(self.grid.handle, _ptr(xTilde), float(beta), k, self._vecs(rows), eta,
+                                    passive.handle if passive is not None else None), "tp_robust_chain")
+        return rows
+
+
 class Overhang:
     """Overhang (self-support) filter (tp_overhang): the printed density of a part built layer by layer along `build`
     ("+z", "-z", "+y", "-y"; the baseplate lies at the low end for +), and the transpose of its Jacobian."""

@@ -1421,6 +1421,11 @@ extern "C" int tp_elasticity_last_op_form(const tp_elasticity *e, int *form4) {
 #include "passive.h"
 
 // ===========================================================================
+// robust design: eroded / nominal / dilated projections in one launch
+// ===========================================================================
+#include "robust.h"
+
+// ===========================================================================
 // optimizer step around the path (MMA), SURVEY.md 8(f)-1
 // ===========================================================================
 #include "mma.h"

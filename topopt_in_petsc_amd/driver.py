@@ -16,7 +16,18 @@ import torch
 from . import mpiio
 import ctypes as C
 
-from .api import Filter, Grid, LengthScale, LinearElasticity, LocalVolume, MMA, Overhang, Passive, SolverOptions, _chk, _ptr, check_body_force, passive_labels
+from .api import Filter, Grid, LengthScale, LinearElasticity, LocalVolume, MMA, Overhang, Passive, Robust, SolverOptions, _chk, _ptr, check_body_force, passive_labels
+
+
+def robust_volume_target(volfrac, S_d, S_n):
+    """V_d*, the volume fraction the DILATED design is held to so that the nominal one meets volfrac: the dilated design holds
+    S_d / S_n times the nominal one's material (Wang, Lazarov, Sigmund 2011, section 4)"""
+    return volfrac * S_d / S_n
+
+
+def robust_volume_due(itr, every):
+    """whether V_d* is recomputed in design iteration itr (counted from 1): in the first one and in every every-th"""
+    return itr == 1 or itr % every == 0
 
 
 @dataclass
@@ -112,9 +123,20 @@ class TopOpt:
     # api.passive_labels.  Void elements are held at x = Xmin, xPhys = 0, solid ones at x = Xmax, xPhys = 1; MMA works on the
     # active elements alone, packed; the volume constraint stays the mean over ALL elements (None: none, nothing changes)
     passive: object = None
+    # robust design: robust = (eta_e, eta_n, eta_d), strictly descending inside (0, 1).  xTilde is projected at the
+    # three thresholds with the one beta: xErode, xPhys (the nominal design: output, MND and restart files carry it) and xDilate.
+    # The objective is the ERODED design's compliance -- for fixed loads the worst of the three, so one solve per iteration as
+    # without -- and the volume is held on the DILATED design at V_d* = volfrac S_d / S_n, recomputed in iteration 1 and every
+    # robust_volume_every-th, so that the nominal design meets volfrac.  robust_report = k: every k-th iteration the nominal and
+    # the dilated design are solved as well and the record gains f_real (0: never).  (None: none, nothing changes)
+    robust: tuple = None
+    robust_volume_every: int = 20
+    robust_report: int = 0
     history: list = field(default_factory=list)
 
     def __post_init__(self):
+        if self.robust is not None:
+            self._check_robust()
         if self.overhang is not None and self.overhang not in Overhang.BUILDS:
             raise ValueError("overhang must be None or one of %s, got %r" % (", ".join(sorted(Overhang.BUILDS)), self.overhang))
         if self.body_force is not None:
@@ -200,6 +222,11 @@ class TopOpt:
         self.x = g.elem_vec(self.volfrac)
         self.xTilde, self.xPhys = g.elem_vec(self.volfrac), g.elem_vec(self.volfrac)
         self.xPrint = g.elem_vec(self.volfrac) if self.overhang_filter is not None else self.xPhys
+        self.projector, self.vd_target, self._S = None, None, None
+        if self.robust is not None:
+            self.projector = Robust(g)
+            self.xErode, self.xDilate = g.elem_vec(self.volfrac), g.elem_vec(self.volfrac)
+            self._U_real = {1: None, 2: None}   # the nominal and the dilated design's states, robust_report's warm starts
         self.dfdx, self.dgdx = g.elem_vec(), [g.elem_vec() for _ in range(self.m)]
         # what MMA works on: the fields themselves, or with passive regions the packed vectors of the active elements
         self.regions, n_mma = None, None
@@ -240,6 +267,37 @@ class TopOpt:
             self.ReadRestartFiles(self.restartFileVec, self.restartFileItr, self.restartFileVecSol)
         # main.cc:48
         self._filter_project()
+        if self.robust is not None and self.vd_target is None:
+            self.vd_target = robust_volume_target(self.volfrac, self._S[2], self._S[1])
+
+    def _check_robust(self):
+        """robust mode's refusals; host arithmetic on the parameters, before any device object"""
+        import math
+        try:
+            etas = tuple(float(v) for v in self.robust)
+        except (TypeError, ValueError):
+            raise ValueError("robust: need three thresholds (eta_e, eta_n, eta_d), got %r" % (self.robust,))
+        if len(etas) != 3 or not all(math.isfinite(v) for v in etas) or not 1.0 > etas[0] > etas[1] > etas[2] > 0.0:
+            raise ValueError("robust: need 1 > eta_e > eta_n > eta_d > 0, got %r" % (self.robust,))
+        if not self.projectionFilter:
+            raise ValueError("robust needs projectionFilter=True: the three designs are projections of xTilde")
+        if self.filter == 0:
+            raise ValueError("robust needs a density or PDE filter: the sensitivity filter (filter=0) has no transpose")
+        if self.eta != 0.0 and self.eta != etas[1]:
+            raise ValueError("robust: eta = %r is neither its default nor eta_n = %r (xPhys is the nominal design)" % (self.eta, etas[1]))
+        if isinstance(self.robust_volume_every, bool) or int(self.robust_volume_every) != self.robust_volume_every \
+                or self.robust_volume_every < 1:
+            raise ValueError("robust_volume_every must be a whole number of at least 1")
+        if isinstance(self.robust_report, bool) or int(self.robust_report) != self.robust_report or self.robust_report < 0:
+            raise ValueError("robust_report must be a whole number, 0 for never")
+        if self.body_force is not None:
+            raise ValueError("robust together with body_force is not supported: with a load that grows with the density the "
+                             "eroded design is no longer the worst of the three")
+        for name in ("stress_limit", "local_volume", "frequency_limit", "overhang", "length_scale"):
+            if getattr(self, name) is not None:
+                raise ValueError("robust together with %s is not supported: the constraint would have to choose a realisation" % name)
+        self.robust, self.eta = etas, etas[1]
+        self.robust_volume_every, self.robust_report = int(self.robust_volume_every), int(self.robust_report)
 
     def _check_passive(self):
         """the global label array of `passive`, checked; sets n_active (global) and the active elements' start value _x0.
@@ -276,7 +334,13 @@ class TopOpt:
         return lab
 
     def _filter_project(self):
-        """x -> xTilde -> xPhys (main.cc:48, :98), the passive values imposed on xPhys (xTilde stays as filtered), then xPrint"""
+        """x -> xTilde -> xPhys (main.cc:48, :98), the passive values imposed on xPhys (xTilde stays as filtered), then xPrint; in
+        robust mode x -> xTilde -> (xErode, xPhys, xDilate) and their sums"""
+        if self.projector is not None:   # the filter alone, then the three projections, the passive values and the sums at once
+            self.filt.FilterProject(self.x, self.xTilde, self.xPhys, False)
+            self._S = self.projector.Project(self.xTilde, self.beta, self.robust, [self.xErode, self.xPhys, self.xDilate],
+                                             passive=self.regions, sums=True)
+            return
         self.filt.FilterProject(self.x, self.xTilde, self.xPhys, self.projectionFilter, self.beta, self.eta)
         if self.regions is not None:
             self.regions.Impose([self.xPhys], 0.0, 1.0)
@@ -293,6 +357,29 @@ class TopOpt:
             out.append(v.value)
         return out[0] / out[1]
 
+    def _solve_realisations(self, f_e):
+        """-> [f_e, f_n, f_d]: the nominal and the dilated design solved beside the eroded one, each warm-started from its own
+        states of the last report; the eroded design's states and the physics' records of its solve come back as they were"""
+        ph = self.physics
+        names = ("last_its", "last_rnorm", "last_bnorm", "last_hist", "last_solve_s", "last_f_case")
+        kept = {k: getattr(ph, k) for k in names if hasattr(ph, k)}
+        lists = {k: list(getattr(ph, k)) for k in ("case_its", "case_rnorm", "case_bnorm")}
+        U_e = [ph.LoadCaseU(c).clone() for c in range(ph.ncases)]
+        out = [f_e]
+        for k, field in ((1, self.xPhys), (2, self.xDilate)):
+            if self._U_real[k] is not None:
+                for c, u in enumerate(self._U_real[k]):
+                    ph.LoadCaseU(c).copy_(u)
+            out.append(ph.ComputeObjectiveConstraints(field, self.Emin, self.Emax, self.penal, self.volfrac)[0])
+            self._U_real[k] = [ph.LoadCaseU(c).clone() for c in range(ph.ncases)]
+        for c, u in enumerate(U_e):
+            ph.LoadCaseU(c).copy_(u)
+        for k, v in kept.items():
+            setattr(ph, k, v)
+        for k, v in lists.items():
+            getattr(ph, k)[:] = v
+        return out
+
     def _print(self):
         """xPrint follows every FilterProject"""
         if self.overhang_filter is not None:
@@ -303,7 +390,16 @@ class TopOpt:
         self.itr += 1
         t1 = time.perf_counter()
         fx, gx = self.physics.ComputeObjectiveConstraintsSensitivities(
-            self.dfdx, self.dgdx[0], self.xPrint, self.Emin, self.Emax, self.penal, self.volfrac)   # main.cc:62
+            self.dfdx, self.dgdx[0], self.xPrint if self.robust is None else self.xErode, self.Emin, self.Emax, self.penal,
+            self.volfrac)                                                                        # main.cc:62
+        if self.robust is not None:   # the volume on the dilated design, against V_d*
+            S, n_glob = list(self._S), self.grid.part.n_own_elems * self.nranks
+            if robust_volume_due(self.itr, self.robust_volume_every):
+                self.vd_target = robust_volume_target(self.volfrac, S[2], S[1])
+            gx = S[2] / (n_glob * self.vd_target) - 1.0
+            self.dgdx[0].fill_(1.0 / (n_glob * self.vd_target))
+            if self.robust_report and self.itr % self.robust_report == 0:
+                f_real = self._solve_realisations(fx)
         if self.body_force is not None:   # (before xPrint moves on)
             body_share = self._body_share()
         if self.itr == 1:
@@ -345,9 +441,13 @@ class TopOpt:
                 gxs.extend(g_length)
         if self.overhang_filter is not None:   # d/dxPrint -> d/dxPhys, all of them in one sweep
             self.overhang_filter.Adjoint([self.dfdx] + rows)
-        if self.regions is not None:   # the rows are d/dxPhys now, and xPhys does not move on passive elements
-            self.regions.Zero([self.dfdx] + rows)
-        self.filt.Gradients(self.x, self.xTilde, self.dfdx, rows, self.projectionFilter, self.beta, self.eta)
+        if self.robust is not None:    # d/dxErode and d/dxDilate -> d/dxTilde, passive entries zeroed, in one launch; then the filter
+            self.projector.Chain(self.xTilde, self.beta, [self.dfdx, self.dgdx[0]], [self.robust[0], self.robust[2]], passive=self.regions)
+            self.filt.GradientsFromTilde(self.x, [self.dfdx, self.dgdx[0]])
+        else:
+            if self.regions is not None:   # the rows are d/dxPhys now, and xPhys does not move on passive elements
+                self.regions.Zero([self.dfdx] + rows)
+            self.filt.Gradients(self.x, self.xTilde, self.dfdx, rows, self.projectionFilter, self.beta, self.eta)
         if self.lengthscale is not None:
             self.filt.GradientsFromTilde(self.x, lrows)
         if self.regions is not None:   # the active entries of the objective's row and every constraint's, one launch
@@ -390,6 +490,10 @@ class TopOpt:
             rec["body_share"] = body_share
         if self.regions is not None:
             rec["n_active"] = self.n_active
+        if self.robust is not None:   # of the design fx and gx belong to
+            rec["vol_real"], rec["vol_dilated_target"] = [v / n_glob for v in S], self.vd_target
+            if self.robust_report and self.itr % self.robust_report == 0:
+                rec["f_real"] = f_real
         self.history.append(rec)
         if verbose and self.rank == 0:
             print("It.: %i, True fx: %f, Scaled fx: %f, gx[0]: %f, ch.: %f, mnd.: %f, time: %f"
@@ -440,13 +544,20 @@ class TopOpt:
         prefix = os.path.join(self.workdir, "Restart" + tag)
         if self.rank == 0:
             mpiio.write_restart(prefix, self.itr, self.fscale, *vecs)
+            if self.robust is not None:   # V_d* is part of the loop's state between its updates: a third number, all digits
+                with open(prefix + "_itr_f0.dat", "w") as f:
+                    f.write("%d  %e  %.17e\n" % (self.itr, self.fscale, self.vd_target))
             mpiio.write_petsc_vecs(os.path.join(self.workdir, "RestartSol%s.dat" % tag), sols)
         return prefix
 
     def ReadRestartFiles(self, vecfile, itrfile, solfile=None):
         """TopOpt::AllocateMMAwithRestart (TopOpt.cc:474-507); solfile = -restartFileVecSol (LinearElasticity.cc:590-606)"""
         x, xPhys, xo1, xo2, U, L = mpiio.read_petsc_vecs(vecfile)
-        itr, fscale = open(itrfile).read().split()
+        if self.robust is None:
+            itr, fscale = open(itrfile).read().split()
+        else:   # a file of a run without `robust` has two numbers: V_d* then comes from the design that was read
+            itr, fscale, *vd = open(itrfile).read().split()
+            self.vd_target = float(vd[0]) if vd else None
         self.x.copy_(self._own(x))
         self.xPhys.copy_(self._own(xPhys))
         self.fscale = float(fscale)

@@ -206,12 +206,16 @@ SYMBOLS = {
     "tp_passive_zero": (_i, [_vp, _i, C.POINTER(_vp)]),
     "tp_passive_gather": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp)]),
     "tp_passive_scatter": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp)]),
+    "tp_robust_project": (_i, [_vp, _vp, _d, _i, C.POINTER(_d), C.POINTER(_vp), _vp, C.POINTER(_d)]),
+    "tp_robust_chain": (_i, [_vp, _vp, _d, _i, C.POINTER(_vp), C.POINTER(_d), _vp]),
 }
 
 
 ABI_VERSION = 4   # TP_ABI_VERSION of include/topopt_amd.h
 MAX_CASES = 8     # TP_MAX_CASES: load cases of one tp_elasticity_response call
 PASSIVE_MAXVEC = 12   # TP_PASSIVE_MAXVEC: vectors of one tp_passive_impose / zero / gather / scatter call
+ROBUST_MAXPROJ = 3    # TP_ROBUST_MAXPROJ: fields of one tp_robust_project call, distinct thresholds of one tp_robust_chain call
+ROBUST_MAXROWS = 8    # TP_ROBUST_MAXROWS: rows of one tp_robust_chain call
 
 
 def load_library():
