@@ -399,6 +399,58 @@ int tp_elasticity_last_stats(const tp_elasticity *e, double *alg_bytes, double *
  * 3 = 32x16, stencil: 1 = node form; [3] fine and level 1: z-chunk length, stencil: 1 = mirrored reads */
 int tp_elasticity_last_op_form(const tp_elasticity *e, int *form4);
 
+/* ---- steady heat conduction ------------------------------------------------
+ * The scalar problem  A(k) T = N q,  A = N K(k) N + (I - N):  one conductivity per element, k_e = kmin + x_e^penal (kmax - kmin),
+ * the element matrix KT = int grad N_a . grad N_b of the grid's box element (8 x 8, reference corner order), N a 0/1 vector
+ * per local node (0: heat sink, T = 0).  Solved like the elasticity problem: CG preconditioned by one multigrid V-cycle with
+ * Chebyshev-Jacobi smoothing, the fine level applied from the conductivities, every coarser level a true Galerkin product
+ * P^T A P stored as 27 diagonals, the coarsest one a Chebyshev run of ncoarse steps over its whole spectrum (coarse_direct is
+ * ignored).  tp_solver_opts as for elasticity (nu unused); ksp_mode 1 is TP_ERR_ARG at creation, and so is a mesh that does not
+ * coarsen nlvls - 1 times or a slab too thin for it.
+ * Every call answers TP_ERR_ARG -- before the handle or the grid is touched -- for a NULL handle or vector, kmin <= 0,
+ * kmax <= kmin, penal < 1, any non-finite parameter, ncase outside 1..TP_MAX_CASES, a level the hierarchy does not have; and
+ * TP_ERR_STATE before set_bc (assemble, response) or before assemble (apply, solve, the level calls). */
+typedef struct tp_conduction tp_conduction;
+int tp_conduction_create(tp_conduction **c, tp_grid *g, const tp_solver_opts *o);
+int tp_conduction_destroy(tp_conduction *c);                    /* NULL: TP_OK */
+int tp_conduction_get_ke(const tp_conduction *c, double *kt_host_64);
+int tp_conduction_set_bc(tp_conduction *c, const double *N /*[dev, local nodes], 0/1*/);
+int tp_conduction_assemble(tp_conduction *c, const double *xPhys /*[dev, own elements]*/, double kmin, double kmax, double penal);
+int tp_conduction_apply(tp_conduction *c, const double *u, double *y);   /* y = A u, [dev, local nodes] */
+/* the same product as CG forms it, with the fused dot product: *dot (host) = u . y over all ranks; dot NULL: nothing is read
+ * back and the host does not wait */
+int tp_conduction_apply_dot(tp_conduction *c, const double *u, double *y, double *dot);
+/* RHS .* N is solved for (as tp_elasticity_solve does it), warm-started from T; its / rnorm / bnorm / hist as there */
+int tp_conduction_solve(tp_conduction *c, const double *RHS, double *T, int *its, double *rnorm, double *bnorm, double *hist,
+                        int hist_cap);
+/* tp_elasticity_response's contract with 8-vectors:  f_case[l] = sum_e k_e v_e^T KT t_e (V[l] NULL: v = t, the thermal compliance of
+ * case l),  *fx = sum_l w_l f_case[l],  *gx = sum x / n_elements - volfrac,  dfdx_e = -penal x^(penal-1) (kmax - kmin) sum_l w_l v_e^T KT t_e,
+ * dgdx = 1 / n_elements.  One pass over the elements, one reduction, one host read; with f_case, fx and gx all NULL nothing is
+ * reduced and the host does not wait.  The ghost planes of every distinct T[l], V[l] are refreshed first. */
+int tp_conduction_response(tp_conduction *c, int ncase,
+        const double *const *T,   /* host array of ncase [dev] pointers, local nodes each              */
+        const double *const *V,   /* NULL, or ncase entries, each NULL (= T[l]) or a [dev] vector       */
+        const double *w,          /* host, ncase weights; NULL = all 1                                  */
+        const double *xPhys, double kmin, double kmax, double penal, double volfrac,
+        double *f_case, double *fx, double *gx, double *dfdx, double *dgdx);
+int tp_conduction_set_tolerances(tp_conduction *c, double rtol, double atol, double dtol, int max_it);   /* negative: keep */
+/* the hierarchy level by level, as the tp_elasticity_ calls of the same names; vectors [dev, the level's local nodes].
+ * level_count / level_nodes answer -TP_ERR_ARG, the lambdas NaN, where the others answer TP_ERR_ARG. */
+int tp_conduction_level_count(const tp_conduction *c);
+long tp_conduction_level_nodes(const tp_conduction *c, int level);
+double tp_conduction_level_lambda(const tp_conduction *c, int level);
+double tp_conduction_level_lambda_min(const tp_conduction *c, int level);
+int tp_conduction_level_apply(tp_conduction *c, int level, const double *u, double *y);
+int tp_conduction_level_diag(tp_conduction *c, int level, double *dinv);
+int tp_conduction_smooth(tp_conduction *c, int level, const double *b, double *x, int k, int zero_guess);
+int tp_conduction_level_residual(tp_conduction *c, int level, const double *b, const double *x, double *r);
+int tp_conduction_restrict(tp_conduction *c, int level, const double *rf, double *rc);
+int tp_conduction_prolong_add(tp_conduction *c, int level, const double *xc, double *xf);
+/* form4 as tp_elasticity_last_op_form; the fine level is a per-node kernel ([0] = 3) with [1] = 2 for the register form of
+ * conduction.h and 0 for the gather over the elements (TP_NO_COND_STENCIL set) */
+int tp_conduction_last_op_form(const tp_conduction *c, int *form4);
+int tp_conduction_last_stats(const tp_conduction *c, double *alg_bytes, double *flops, long *kernel_launches);
+
 /* ---- density / sensitivity filter (Filter.cc) --------------------------- */
 typedef struct tp_filter tp_filter;
 /* Filter::Filter + SetUp (Filter.cc:25-38, :290-463).  filterType 0 = sensitivity,

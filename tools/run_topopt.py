@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """End-to-end run of the reference's optimisation loop on the MI355X path.
-usage: run_topopt.py [--loadcase top[:weight]]... [--stress-limit L [--stress-p P] [--stress-q q]] [--local-volume ALPHA:R] [--overhang +z|-z|+y|-y] [--self-weight bx,by,bz[:xlow] [--no-point-load]] [--length-scale both|solid|void[:C]] [--frequency-limit L[:nev]] [--passive solid|void:box|sphere|cylinder:numbers]... [--robust ETA_E,ETA_N,ETA_D[:every]] ex ey ez nlvls n_iter [filter [nsmooth ncoarse]]
+usage: run_topopt.py [--physics elasticity|heat] [--loadcase top[:weight]]... [--stress-limit L [--stress-p P] [--stress-q q]] [--local-volume ALPHA:R] [--overhang +z|-z|+y|-y] [--self-weight bx,by,bz[:xlow] [--no-point-load]] [--length-scale both|solid|void[:C]] [--frequency-limit L[:nev]] [--passive solid|void:box|sphere|cylinder:numbers]... [--robust ETA_E,ETA_N,ETA_D[:every]] ex ey ez nlvls n_iter [filter [nsmooth ncoarse]]
 (e.g. 128 128 128 5 20 1 2 45: the cycle of bench.py; --loadcase top:0.5 adds the line load on the upper edge as a second load
 case of weight 0.5 -- the objective becomes the weighted sum of the cases' compliances; --stress-limit L holds the von Mises
 p-norm of load case 0 below L as a second constraint, exponent --stress-p (8), stress relaxation x^q with --stress-q (0.5); --local-volume ALPHA:R holds the mean density in a ball of
@@ -16,7 +16,10 @@ regions of DESIGN 4.15, in physical coordinates (the box is ex/ey x 1 x ez/ey): 
 cylinder:axis,c1,c2,r (axis x, y or z, infinite along it); later shapes override earlier ones, e.g.
 --passive solid:box:1.9,2,0,1,0,0.1 --passive void:sphere:1,0.5,0.5,0.25; --robust 0.7,0.5,0.3[:every] runs the robust formulation of
 DESIGN 4.16 with the Heaviside projection switched on: the compliance of the design eroded at 0.7, the volume held on the design
-dilated at 0.3 so that the nominal one at 0.5 meets volfrac, the dilated target recomputed every `every` (20) iterations)"""
+dilated at 0.3 so that the nominal one at 0.5 meets volfrac, the dilated target recomputed every `every` (20) iterations;
+--physics heat runs the heat-sink problem of DESIGN 4.17 instead of the cantilever: steady conduction with a sink patch on the face
+x = 0 and a uniform source, conductivity 1e-3 + xPhys^3 (1 - 1e-3), the thermal compliance as the objective -- with --passive
+only, none of the other options)"""
 import os
 import sys
 
@@ -108,13 +111,16 @@ if robust_arg is not None:
         robust = dict(robust=tuple(float(v) for v in etas.split(",")), robust_volume_every=int(every) if every else 20, projectionFilter=True)
     except ValueError:
         sys.exit("--robust needs ETA_E,ETA_N,ETA_D[:every], e.g. 0.7,0.5,0.3:20, got %r" % robust_arg)
+physics = _last("--physics") or "elasticity"
+if physics not in ("elasticity", "heat"):
+    sys.exit("--physics needs elasticity or heat, got %r" % physics)
 ex, ey, ez, nlv, nit = [int(v) for v in sys.argv[1:6]]
 flt = int(sys.argv[6]) if len(sys.argv) > 6 else 1
 h = 1.0 / ey
 opt = tp.TopOpt(nxyz=(ex + 1, ey + 1, ez + 1), xc=(0, ex * h, 0, 1, 0, ez * h), nlvls=nlv, rmin=2.56 * h, filter=flt,
-                loadcases=loadcases or None, **stress, **local, overhang=overhang, **body, **length, **frequency, passive=shapes or None, **robust,
+                loadcases=loadcases or None, **stress, **local, overhang=overhang, **body, **length, **frequency, passive=shapes or None, **robust, physics=physics,
                 solver=tp.SolverOptions(nlvls=nlv, **(dict(nsmooth=int(sys.argv[7]), ncoarse=int(sys.argv[8])) if len(sys.argv) > 8 else {})))
-print("# %dx%dx%d elements, %d DOF, %d MG levels, filter %d, rmin %.4f" % (ex, ey, ez, 3 * (ex + 1) * (ey + 1) * (ez + 1), nlv, flt, 2.56 * h))
+print("# %dx%dx%d elements, %d DOF, %d MG levels, filter %d, rmin %.4f" % (ex, ey, ez, (1 if physics == "heat" else 3) * (ex + 1) * (ey + 1) * (ez + 1), nlv, flt, 2.56 * h))
 for it in range(nit):
     r = opt.step(verbose=True)
     print("State solver:  iter: %i, rerr.: %e | MMA inner its: %d" % (r["ksp_its"], r["ksp_rerr"], r["mma_inner"]), flush=True)

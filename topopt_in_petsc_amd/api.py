@@ -892,6 +892,194 @@ class LinearElasticity:
         return tuple(f)
 
 
+def heat_sink_and_load(nx, ny, nz, h, q0=1.0, node_z0=0, nz_local=None):
+    """The built-in heat-sink problem on nx x ny x nz nodes (global counts), planes [node_z0, node_z0 + nz_local) of it, as
+    torch CPU tensors (N, RHS) in the local node layout.  Sink (N = 0): the nodes of the face i = 0 with
+    |2j - (ny-1)| <= max(1, (ny-1)//4) and |2k - (nz-1)| <= max(1, (nz-1)//4), never empty.  Load: a uniform volumetric source,
+    rhs_n = q0 hx hy hz / 8 x (number of elements around node n)."""
+    nzl = nz if nz_local is None else nz_local
+    hx, hy, hz = (h, h, h) if isinstance(h, (int, float)) else tuple(h)
+    j, k = torch.arange(ny), torch.arange(nzl) + node_z0
+    sj = (2 * j - (ny - 1)).abs() <= max(1, (ny - 1) // 4)
+    sk = (2 * k - (nz - 1)).abs() <= max(1, (nz - 1) // 4)
+    N = torch.ones(nzl, ny, nx, dtype=torch.float64)
+    N[:, :, 0] = 1.0 - (sk[:, None] & sj[None, :]).to(torch.float64)
+    around = lambda idx, n: torch.where((idx == 0) | (idx == n - 1), 1.0, 2.0).to(torch.float64)
+    cnt = around(k, nz)[:, None, None] * around(j, ny)[None, :, None] * around(torch.arange(nx), nx)[None, None, :]
+    return N.reshape(-1), (q0 * hx * hy * hz / 8.0 * cnt).reshape(-1)
+
+
+class HeatConduction:
+    """Steady heat conduction on the MI355X (include/topopt_amd.h: tp_conduction): conductivity k = kmin + x^p (kmax - kmin) per
+    element, temperature T per node, heat sink where N = 0.  Methods are named as on LinearElasticity."""
+
+    def __init__(self, grid, opts=None):
+        self.grid, self.L = grid, grid.L
+        self.opts = opts or SolverOptions()
+        self.handle = C.c_void_p()
+        self._o = self.opts.c_struct()
+        _chk(self.L.tp_conduction_create(C.byref(self.handle), grid.handle, C.byref(self._o)), "tp_conduction_create")
+        grid._adopt(self)
+        self.T = grid.node_vec(1)       # state, persists across design iterations (warm start)
+        self.RHS = grid.node_vec(1)
+        self.N = grid.node_vec(1)
+        self.last_its, self.last_rnorm, self.last_bnorm, self.last_hist = 0, 0.0, 0.0, None
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.L.tp_conduction_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    ncases = 1   # one load, one state: what the driver's records and restart files ask a physics object for
+
+    def LoadCaseU(self, case):
+        return self.T
+
+    @property
+    def KT(self):
+        import numpy as np
+        kt = np.zeros(64)
+        _chk(self.L.tp_conduction_get_ke(self.handle, kt.ctypes.data), "tp_conduction_get_ke")
+        return kt
+
+    def SetUpLoadAndBC(self, q0=1.0):
+        """the built-in heat-sink problem (heat_sink_and_load); single rank or z-slabs (global z index decides; the load on the
+        owned planes only)"""
+        p = self.grid.part
+        N, R = heat_sink_and_load(p.nx, p.ny, p.nz, self.grid.h, q0, p.node_z0, p.nz_local)
+        off, own = self.L.tp_grid_owned_node_offset(self.grid.handle), self.L.tp_grid_owned_nodes(self.grid.handle)
+        R[:off] = 0.0
+        R[off + own:] = 0.0
+        self.SetBC(N.to(self.T.device), R.to(self.T.device))
+
+    def SetBC(self, N, RHS):
+        self.N.copy_(N)
+        self.RHS.copy_(RHS)
+        _chk(self.L.tp_conduction_set_bc(self.handle, _ptr(self.N)), "tp_conduction_set_bc")
+
+    def SetTolerances(self, rtol=-1.0, atol=-1.0, dtol=-1.0, max_it=-1):
+        _chk(self.L.tp_conduction_set_tolerances(self.handle, float(rtol), float(atol), float(dtol), int(max_it)), "tp_conduction_set_tolerances")
+        for name, v in (("rtol", rtol), ("atol", atol), ("dtol", dtol), ("max_it", max_it)):
+            if v >= 0:
+                setattr(self.opts, name, type(getattr(self.opts, name))(v))
+
+    def AssembleConductivityMatrix(self, xPhys, kmin, kmax, penal):
+        _chk(self.L.tp_conduction_assemble(self.handle, _ptr(xPhys), kmin, kmax, penal), "tp_conduction_assemble")
+
+    def MatMult(self, u, y=None):
+        y = torch.zeros_like(u) if y is None else y
+        _chk(self.L.tp_conduction_apply(self.handle, _ptr(u), _ptr(y)), "tp_conduction_apply")
+        return y
+
+    def MatMultDot(self, u, y=None, read=True):
+        """the product as CG forms it, with its fused dot product -> (y, u . y); read=False: (y, None), the host does not wait"""
+        y = torch.zeros_like(u) if y is None else y
+        d = C.c_double()
+        _chk(self.L.tp_conduction_apply_dot(self.handle, _ptr(u), _ptr(y), C.byref(d) if read else None), "tp_conduction_apply_dot")
+        return y, (d.value if read else None)
+
+    def KSPSolve(self, hist_cap=0, rhs=None):
+        """solve on the last assembly, warm-started from self.T (rhs: another right-hand side than self.RHS)"""
+        import time
+        import numpy as np
+        its, rn, bn = C.c_int(), C.c_double(), C.c_double()
+        hist = np.zeros(max(hist_cap, 1))
+        t0 = time.perf_counter()   # the solve ends with a host read of ||r||: wall time == device time
+        rc = self.L.tp_conduction_solve(self.handle, _ptr(self.RHS if rhs is None else rhs), _ptr(self.T), C.byref(its), C.byref(rn),
+                                        C.byref(bn), hist.ctypes.data if hist_cap else None, hist_cap)
+        self.last_solve_s = time.perf_counter() - t0
+        self.last_its, self.last_rnorm, self.last_bnorm = its.value, rn.value, bn.value
+        self.last_hist = hist[: min(its.value + 1, hist_cap)] if hist_cap else None
+        _chk(rc, "tp_conduction_solve")
+        return its.value
+
+    def SolveState(self, xPhys, kmin, kmax, penal, hist_cap=0):
+        self.AssembleConductivityMatrix(xPhys, kmin, kmax, penal)
+        return self.KSPSolve(hist_cap)
+
+    def Response(self, T_list, V_list, w, xPhys, kmin, kmax, penal, volfrac, dfdx=None, dgdx=None, sums=True):
+        """tp_conduction_response: fx = sum_l w_l f_l with f_l = sum_e k_e v_l^T KT t_l, gx, dfdx, dgdx for all cases in one pass
+        over the elements -> (fx, gx, f_case).  V_list None, or an entry None: V_l = T_l (thermal compliance); w None: all
+        weights 1.  sums=False: nothing is reduced and the host does not wait -> (None, None, None)."""
+        n = len(T_list)
+        Ta = (C.c_void_p * max(n, 1))(*[_ptr(t) for t in T_list])
+        Va = None if V_list is None else (C.c_void_p * max(n, 1))(*[_ptr(v) for v in V_list])
+        wa = None if w is None else (C.c_double * max(n, 1))(*[float(v) for v in w])
+        fx, gx, fc = C.c_double(), C.c_double(), (C.c_double * max(n, 1))()
+        _chk(self.L.tp_conduction_response(self.handle, n, Ta, Va, wa, _ptr(xPhys), kmin, kmax, penal, volfrac,
+                                           fc if sums else None, C.byref(fx) if sums else None, C.byref(gx) if sums else None,
+                                           _ptr(dfdx), _ptr(dgdx)), "tp_conduction_response")
+        return (fx.value, gx.value, list(fc)[:n]) if sums else (None, None, None)
+
+    def ComputeObjectiveConstraintsSensitivities(self, dfdx, dgdx, xPhys, kmin, kmax, penal, volfrac, hist_cap=0):
+        """solve, then the thermal compliance fx = T^T K T, the volume constraint gx and their sensitivities -> (fx, gx)"""
+        self.SolveState(xPhys, kmin, kmax, penal, hist_cap)
+        fx, gx, _ = self.Response([self.T], None, None, xPhys, kmin, kmax, penal, volfrac, dfdx, dgdx)
+        return fx, gx
+
+    # ---- introspection used by the tests ----------------------------
+    def level_count(self):
+        return self.L.tp_conduction_level_count(self.handle)
+
+    def level_nodes(self, l):
+        return self.L.tp_conduction_level_nodes(self.handle, l)
+
+    def level_lambda(self, l):
+        return self.L.tp_conduction_level_lambda(self.handle, l)
+
+    def level_lambda_min(self, l):
+        return self.L.tp_conduction_level_lambda_min(self.handle, l)
+
+    def level_vec(self, l):
+        return torch.zeros(self.level_nodes(l), dtype=torch.float64, device=self.grid.device)
+
+    def level_apply(self, l, u):
+        y = torch.zeros_like(u)
+        _chk(self.L.tp_conduction_level_apply(self.handle, l, _ptr(u), _ptr(y)), "tp_conduction_level_apply")
+        return y
+
+    def level_dinv(self, l):
+        d = self.level_vec(l)
+        _chk(self.L.tp_conduction_level_diag(self.handle, l, _ptr(d)), "tp_conduction_level_diag")
+        return d
+
+    def smooth(self, l, b, x, k, zero_guess=False):
+        _chk(self.L.tp_conduction_smooth(self.handle, l, _ptr(b), _ptr(x), k, int(zero_guess)), "tp_conduction_smooth")
+        return x
+
+    def level_residual(self, l, b, x):
+        r = torch.zeros_like(x)
+        _chk(self.L.tp_conduction_level_residual(self.handle, l, _ptr(b), _ptr(x), _ptr(r)), "tp_conduction_level_residual")
+        return r
+
+    def restrict(self, l, rf):
+        rc = self.level_vec(l + 1)
+        _chk(self.L.tp_conduction_restrict(self.handle, l, _ptr(rf), _ptr(rc)), "tp_conduction_restrict")
+        return rc
+
+    def prolong_add(self, l, xc, xf):
+        _chk(self.L.tp_conduction_prolong_add(self.handle, l, _ptr(xc), _ptr(xf)), "tp_conduction_prolong_add")
+        return xf
+
+    def pop_stats(self):
+        b, f, n = C.c_double(), C.c_double(), C.c_long()
+        self.L.tp_conduction_last_stats(self.handle, C.byref(b), C.byref(f), C.byref(n))
+        return b.value, f.value, n.value
+
+    def last_op_form(self):
+        """(kind, a, b, c) of the last operator application: kind 3 per-node kernel (a = 2: the register form of conduction.h,
+        0: the gather over the elements), 4 stored stencil (threads per row, node form, mirrored reads)"""
+        f = (C.c_int * 4)()
+        _chk(self.L.tp_conduction_last_op_form(self.handle, f), "tp_conduction_last_op_form")
+        return tuple(f)
+
+
 class Filter:
     """Filter (Filter.h:34-92): filterType 0 sensitivity, 1 density, 2 PDE."""
 

@@ -148,3 +148,26 @@ inline void helmholtz_element_box(double dx, double dy, double dz, double RR, do
         for (int q = 0; q < 8; q++)
             KF[8 * p + q] = v[(lx[p] != lx[q]) + 2 * (ly[p] != ly[q]) + 4 * (lz[p] != lz[q])];
 }
+
+// Conduction element matrix KT = int grad N_a . grad N_b on a box element at unit conductivity, closed form: the tensor sum
+// Sx (x) My (x) Mz + Mx (x) Sy (x) Mz + Mx (x) My (x) Sz of the 1-D stiffness S = [[1, -1], [-1, 1]] / h and mass
+// M = h [[2, 1], [1, 2]] / 6 per axis -- the gradient part of helmholtz_element_box, (KF(R = 2) - KF(R = 1)) / 3.  Like KF its
+// entries depend only on the axes along which the two corners differ: v8[dx + 2 dy + 4 dz] (optional) holds the 8 values.
+inline void conduction_element_box(double dx, double dy, double dz, double *KT /*64*/, double *v8 = nullptr) {
+    const double h[3] = {dx, dy, dz};
+    double S[3][2], M[3][2];  // [axis][corners differ along it]
+    for (int d = 0; d < 3; d++) {
+        S[d][0] = 1.0 / h[d], S[d][1] = -1.0 / h[d];
+        M[d][0] = h[d] / 3.0, M[d][1] = h[d] / 6.0;
+    }
+    double v[8];
+    for (int q = 0; q < 8; q++) {
+        const int x = q & 1, y = (q >> 1) & 1, z = q >> 2;
+        v[q] = S[0][x] * M[1][y] * M[2][z] + M[0][x] * S[1][y] * M[2][z] + M[0][x] * M[1][y] * S[2][z];
+    }
+    const int lx[8] = {0, 1, 1, 0, 0, 1, 1, 0}, ly[8] = {0, 0, 1, 1, 0, 0, 1, 1}, lz[8] = {0, 0, 0, 0, 1, 1, 1, 1};
+    for (int p = 0; p < 8; p++)
+        for (int q = 0; q < 8; q++) KT[8 * p + q] = v[(lx[p] != lx[q]) + 2 * (ly[p] != ly[q]) + 4 * (lz[p] != lz[q])];
+    if (v8)
+        for (int q = 0; q < 8; q++) v8[q] = v[q];
+}

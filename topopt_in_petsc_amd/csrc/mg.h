@@ -18,6 +18,7 @@
 #include "galerkin.h"
 #include "grid.h"
 #include "operators.h"
+#include "conduction.h"
 #include "coarse_run.h"
 #include "matfree_tile.h"
 #include "fine_tile.h"
@@ -57,6 +58,8 @@ struct Level {
     double *corr = nullptr;           // [dev] level dofs, zero outside the affected nodes
     const uint8_t *colmask = nullptr; // [dev] per node column: OR of mask over z
     const double *wtab = nullptr;     // [dev] DOF == 1, constant coefficients: 27 x 27 stencil table (operators.h: ScalarStencilOp)
+    const unsigned *nbmask = nullptr; // [dev] DOF == 1, one coefficient per element and Dirichlet rows: mask bits of a node's 27 neighbours (conduction.h: ConductionOp)
+    double kt8[8] = {};               // ... and the 8 distinct entries of its element matrix
     long ndof() const { return (long)DOF * g.nodes(); }
     long own_off() const { return (long)DOF * g.plane() * g.own_lo; }
     long own_n() const { return (long)DOF * g.owned_nodes(); }
@@ -106,7 +109,8 @@ struct MGSolver {
     int last_nblocks = 0;  // workgroups (= reduction partials) of the last op<EPI_APPLY_DOT>
     // what the last op<>() launched, for the tests (tp_elasticity_last_op_form): [0] 1 fine tile kernel, 2 level 1 from the fine
     // densities, 3 per-node matrix-free, 4 stored stencil; [1] fine: generation, level 1: correction fused, per-node: 1 = the scalar
-    // operator's 27-point table (ScalarStencilOp), 0 = the gather over the elements, stencil: row split;
+    // operator's 27-point table (ScalarStencilOp), 2 = the conduction operator from registers (ConductionOp), 0 = the gather over
+    // the elements (MatfreeOp), stencil: row split;
     // [2] fine: tile 0 15 x 15 nodes, 1 16x16, 2 32x8, 3 32x16, stencil: node form; [3] fine, level 1: z-chunk, stencil: mirrored reads
     int last_form[4] = {0, 0, 0, 0};
     static constexpr int NLANCZOS_COARSE = 40;

@@ -241,12 +241,12 @@ int MGSolver<DOF>::op_macro(OpLaunch &c, const NodeArgs &a) {
 }
 
 // A matrix-free level without a tuned kernel: a thread per node (k_node); the constant-coefficient scalar operator of
-// DOF 1 in its 27-point stencil form
+// DOF 1 in its 27-point stencil form, the variable-coefficient one (conduction) from registers
 template <int DOF>
 template <int EPI>
 int MGSolver<DOF>::op_matfree_node(OpLaunch &c, const NodeArgs &a) {
     Level<DOF> &L = lv[c.l];
-    bool as_stencil = false;
+    bool as_stencil = false, cond_form = false;
     if constexpr (DOF == 1) {
         if (L.wtab && !L.E && !L.mask && !sw_no_pde_stencil()) {   // constant-coefficient scalar operator: its 27-point stencil form
             ScalarStencilOp so{L.wtab, L.g};
@@ -254,6 +254,14 @@ int MGSolver<DOF>::op_matfree_node(OpLaunch &c, const NodeArgs &a) {
             c.bytes = 16.0 * c.nown;
             c.flops = 2.0 * 27 * (double)c.nown;
             as_stencil = true;
+        } else if (L.nbmask && L.E && !sw_no_cond_stencil()) {   // one coefficient per element, Dirichlet rows: 27 values + 8 coefficients from registers
+            ConductionOp co{L.E, L.nbmask, {}, L.g};
+            for (int q = 0; q < 8; q++) co.v[q] = L.kt8[q];
+            TP_LAUNCH((k_node<1, ConductionOp, EPI>), dim3(c.nb), dim3(BLK), 0, grid->stream, co, a);
+            c.bytes = 16.0 * c.nown + 8.0 * L.g.own_elems();
+            c.flops = 2.0 * 72 * (double)c.nown;
+            as_stencil = true;
+            cond_form = true;
         }
     }
     if (!as_stencil) {
@@ -262,7 +270,7 @@ int MGSolver<DOF>::op_matfree_node(OpLaunch &c, const NodeArgs &a) {
         c.bytes = 16.0 * DOF * c.nown + (L.E ? 8.0 * L.g.own_elems() : 0.0);
         c.flops = 2.0 * (8 * DOF) * (8 * DOF) * (double)L.g.own_elems();
     }
-    last_form[0] = 3, last_form[1] = as_stencil ? 1 : 0, last_form[2] = last_form[3] = 0;
+    last_form[0] = 3, last_form[1] = cond_form ? 2 : (as_stencil ? 1 : 0), last_form[2] = last_form[3] = 0;
     return TP_OK;
 }
 
@@ -285,7 +293,8 @@ int MGSolver<DOF>::op_stencil(OpLaunch &c, const NodeArgs &a) {
     // (one thread over all 27 neighbours) measured 209 / 387 us: too many registers per thread to keep the stream busy.
     const bool by_node = sw_dia_node();
     const int rsplit = split_env >= 0 ? split_env : (nbr_all < 128 ? 9 : ((DOF == 3 && by_node) ? 3 : (nbr_all < 512 ? 3 : 1)));
-    const bool sym = !sw_no_dia_sym();
+    // (the mirrored reads come with a row-sum correction that exists for DOF 3 only: a scalar stencil level reads its own rows)
+    const bool sym = DOF == 3 && !sw_no_dia_sym();
     auto launch_rows = [&](long t0, long tn, long t1, long tn1) -> int {
         o.t0 = t0, o.tn = tn, o.t1 = t1, o.tn1 = tn1;
         const long rows = tn < 0 ? rows_all : tn + tn1;

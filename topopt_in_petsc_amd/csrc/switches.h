@@ -273,6 +273,9 @@ inline bool sw_overlap() { return sw_not_zero("TP_OVERLAP"); }
 inline bool sw_no_tile() { return sw_set("TP_NO_TILE"); }
 // TP_NO_MACRO set (default on; read per assembly): level 1 as a stored stencil instead of applied from the fine densities
 inline bool sw_no_macro() { return sw_set("TP_NO_MACRO"); }
+// TP_NO_COND_STENCIL set (default register form; read per launch): the conduction operator's fine level through the generic
+// gather MatfreeOp<1> instead of ConductionOp (conduction.h); the same bits either way
+inline bool sw_no_cond_stencil() { return sw_set("TP_NO_COND_STENCIL"); }
 // TP_SMOOTH_GRAPH=1 (default off, and off under TP_DEBUG_SYNC): the coarsest level's smoothing run as a replayed hipGraph (measured 0.3 % SLOWER at 128^3, mg_coarse.h)
 inline bool sw_smooth_graph() {
     const char *e = getenv("TP_SMOOTH_GRAPH");

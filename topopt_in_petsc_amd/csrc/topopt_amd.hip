@@ -1396,6 +1396,11 @@ extern "C" int tp_elasticity_last_op_form(const tp_elasticity *e, int *form4) {
 #include "blockvec.h"
 
 // ===========================================================================
+// steady heat conduction: the scalar solve with one conductivity per element
+// ===========================================================================
+#include "conduction_api.h"
+
+// ===========================================================================
 // density / sensitivity filter and Helmholtz PDE filter
 // ===========================================================================
 #include "filter.h"

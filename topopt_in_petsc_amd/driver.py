@@ -16,7 +16,7 @@ import torch
 from . import mpiio
 import ctypes as C
 
-from .api import Filter, Grid, LengthScale, LinearElasticity, LocalVolume, MMA, Overhang, Passive, Robust, SolverOptions, _chk, _ptr, check_body_force, passive_labels
+from .api import Filter, Grid, HeatConduction, LengthScale, LinearElasticity, LocalVolume, MMA, Overhang, Passive, Robust, SolverOptions, _chk, _ptr, check_body_force, passive_labels
 
 
 def robust_volume_target(volfrac, S_d, S_n):
@@ -132,9 +132,21 @@ class TopOpt:
     robust: tuple = None
     robust_volume_every: int = 20
     robust_report: int = 0
+    # the state problem: "elasticity", or "heat" -- steady conduction with a heat sink and a uniform source (api.
+    # HeatConduction.SetUpLoadAndBC), conductivity kmin + xPhys^penal (kmax - kmin), the thermal compliance as the objective.  The
+    # filter, the projection, MMA, passive regions, restart files and output are used as they are; after construction `physics` is
+    # the solver object, as it always was, and `physics_kind` keeps the name
+    physics: str = "elasticity"
+    kmin: float = 1.0e-3
+    kmax: float = 1.0
     history: list = field(default_factory=list)
 
     def __post_init__(self):
+        self.physics_kind = self.physics
+        if self.physics_kind not in ("elasticity", "heat"):
+            raise ValueError("physics must be 'elasticity' or 'heat', got %r" % (self.physics,))
+        if self.physics_kind == "heat":
+            self._check_heat()
         if self.robust is not None:
             self._check_robust()
         if self.overhang is not None and self.overhang not in Overhang.BUILDS:
@@ -199,8 +211,11 @@ class TopOpt:
         labels = self._check_passive() if self.passive is not None else None
         self.grid = Grid(nx, ny, nz, h, rank=self.rank, nranks=self.nranks)
         so = self.solver or SolverOptions(nlvls=self.nlvls, nu=self.nu)
-        self.physics = LinearElasticity(self.grid, so)
+        self.physics = (HeatConduction if self.physics_kind == "heat" else LinearElasticity)(self.grid, so)
         self.physics.SetUpLoadAndBC()
+        # the material interpolation's end values as the physics takes them
+        self._dof = 1 if self.physics_kind == "heat" else 3
+        self._mat = (self.kmin, self.kmax) if self.physics_kind == "heat" else (self.Emin, self.Emax)
         if self.body_force is not None:
             self.physics.SetBodyForce(self.body_force, self.body_force_xlow)
             self._f_body = self.grid.node_vec(3)
@@ -269,6 +284,21 @@ class TopOpt:
         self._filter_project()
         if self.robust is not None and self.vd_target is None:
             self.vd_target = robust_volume_target(self.volfrac, self._S[2], self._S[1])
+
+    def _check_heat(self):
+        """heat conduction's refusals; host arithmetic on the parameters, before any device object"""
+        import math
+        for name, what in (("loadcases", "further load cases"), ("stress_limit", "the stress constraint"), ("body_force", "self-weight"),
+                           ("frequency_limit", "the eigenfrequency constraint"), ("robust", "robust design"), ("overhang", "the overhang filter"),
+                           ("local_volume", "the local volume constraint"), ("length_scale", "the length-scale constraints")):
+            if getattr(self, name) is not None:
+                raise ValueError("physics='heat' together with %s (%s) is not supported" % (name, what))
+        if not self.point_load:
+            raise ValueError("physics='heat' has no point_load switch: the source is the built-in uniform one")
+        if not (math.isfinite(self.kmin) and math.isfinite(self.kmax) and self.kmin > 0.0 and self.kmax > self.kmin):
+            raise ValueError("physics='heat' needs 0 < kmin < kmax, both finite; got %r, %r" % (self.kmin, self.kmax))
+        if not (math.isfinite(self.penal) and self.penal >= 1.0):
+            raise ValueError("physics='heat' needs penal >= 1, got %r" % (self.penal,))
 
     def _check_robust(self):
         """robust mode's refusals; host arithmetic on the parameters, before any device object"""
@@ -390,7 +420,7 @@ class TopOpt:
         self.itr += 1
         t1 = time.perf_counter()
         fx, gx = self.physics.ComputeObjectiveConstraintsSensitivities(
-            self.dfdx, self.dgdx[0], self.xPrint if self.robust is None else self.xErode, self.Emin, self.Emax, self.penal,
+            self.dfdx, self.dgdx[0], self.xPrint if self.robust is None else self.xErode, self._mat[0], self._mat[1], self.penal,
             self.volfrac)                                                                        # main.cc:62
         if self.robust is not None:   # the volume on the dilated design, against V_d*
             S, n_glob = list(self._S), self.grid.part.n_own_elems * self.nranks
@@ -540,7 +570,7 @@ class TopOpt:
             self.regions.Scatter(packed, [xo1, xo2, U, L])
         vecs = [self._gather(v) for v in (self.x, self.xPhys, xo1, xo2, U, L)]
         # the further cases' states follow the first Vec (the reference's reader takes the first one only)
-        sols = [self._gather(self.physics.LoadCaseU(c)[self.grid.part.owned_slice(3)]) for c in range(self.physics.ncases)]
+        sols = [self._gather(self.physics.LoadCaseU(c)[self.grid.part.owned_slice(self._dof)]) for c in range(self.physics.ncases)]
         prefix = os.path.join(self.workdir, "Restart" + tag)
         if self.rank == 0:
             mpiio.write_restart(prefix, self.itr, self.fscale, *vecs)
@@ -571,15 +601,21 @@ class TopOpt:
             self.mma.SetRestart(self.itr, *state)
         if solfile and os.path.exists(solfile):
             sols = mpiio.read_petsc_vecs(solfile)   # a file with fewer states than cases leaves the others at zero
-            sl = self.grid.part.owned_slice(3)
-            n0 = 3 * self.grid.part.plane * (self.grid.part.node_z0 + self.grid.part.own_lo)
+            sl = self.grid.part.owned_slice(self._dof)
+            n0 = self._dof * self.grid.part.plane * (self.grid.part.node_z0 + self.grid.part.own_lo)
             for c, sol in enumerate(sols[:self.physics.ncases]):
                 U = self.physics.LoadCaseU(c)
                 U.zero_()
                 U[sl] = torch.from_numpy(sol[n0:n0 + (sl.stop - sl.start)].copy()).to(self.x.device)
 
     def WriteVTK(self, itr):
-        if self._out is not None:
+        if self._out is None:
+            return
+        if self.physics_kind == "heat":   # the point field keeps its three components: the temperature in the first
+            U = self.grid.node_vec(3)
+            U[0::3] = self.physics.T
+            self._out.WriteVTK(U, self.x, self.xTilde, self.xPrint, itr)
+        else:
             self._out.WriteVTK(self.physics.U, self.x, self.xTilde, self.xPrint, itr)
 
     def _increase_beta(self, gx, ch):

@@ -208,6 +208,29 @@ SYMBOLS = {
     "tp_passive_scatter": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp)]),
     "tp_robust_project": (_i, [_vp, _vp, _d, _i, C.POINTER(_d), C.POINTER(_vp), _vp, C.POINTER(_d)]),
     "tp_robust_chain": (_i, [_vp, _vp, _d, _i, C.POINTER(_vp), C.POINTER(_d), _vp]),
+    "tp_conduction_create": (_i, [C.POINTER(_vp), _vp, C.POINTER(SolverOpts)]),
+    "tp_conduction_destroy": (_i, [_vp]),
+    "tp_conduction_get_ke": (_i, [_vp, _vp]),
+    "tp_conduction_set_bc": (_i, [_vp, _vp]),
+    "tp_conduction_assemble": (_i, [_vp, _vp, _d, _d, _d]),
+    "tp_conduction_apply": (_i, [_vp, _vp, _vp]),
+    "tp_conduction_apply_dot": (_i, [_vp, _vp, _vp, C.POINTER(_d)]),
+    "tp_conduction_solve": (_i, [_vp, _vp, _vp, C.POINTER(_i), C.POINTER(_d), C.POINTER(_d), _vp, _i]),
+    "tp_conduction_response": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_d), _vp, _d, _d, _d, _d, C.POINTER(_d),
+                                    C.POINTER(_d), C.POINTER(_d), _vp, _vp]),
+    "tp_conduction_set_tolerances": (_i, [_vp, _d, _d, _d, _i]),
+    "tp_conduction_level_count": (_i, [_vp]),
+    "tp_conduction_level_nodes": (_l, [_vp, _i]),
+    "tp_conduction_level_lambda": (_d, [_vp, _i]),
+    "tp_conduction_level_lambda_min": (_d, [_vp, _i]),
+    "tp_conduction_level_apply": (_i, [_vp, _i, _vp, _vp]),
+    "tp_conduction_level_diag": (_i, [_vp, _i, _vp]),
+    "tp_conduction_smooth": (_i, [_vp, _i, _vp, _vp, _i, _i]),
+    "tp_conduction_level_residual": (_i, [_vp, _i, _vp, _vp, _vp]),
+    "tp_conduction_restrict": (_i, [_vp, _i, _vp, _vp]),
+    "tp_conduction_prolong_add": (_i, [_vp, _i, _vp, _vp]),
+    "tp_conduction_last_op_form": (_i, [_vp, C.POINTER(_i)]),
+    "tp_conduction_last_stats": (_i, [_vp, C.POINTER(_d), C.POINTER(_d), C.POINTER(_l)]),
 }
 
 
