@@ -320,6 +320,34 @@ int tp_elasticity_body_load(tp_elasticity *e, const double *xPhys /*[dev, own el
 int tp_elasticity_body_sensitivity(tp_elasticity *e, int ncase, const double *const *V /*host array of [dev] pointers*/,
                             const double *w /*host, NULL = all 1*/, const double *xPhys, const double *b3, double x_low,
                             double scale, double *dfdx /*[dev, own elements], added to*/);
+/* Thermal expansion: a nodal temperature field T loads the structure.  theta = T - T_ref at the nodes; element e pushes on its 24
+ * dofs with beta(x_e) G theta_e, G[(a,c), b] = 1 / (1 - 2 nu) int dN_a/dx_c N_b dV the 24 x 8 coupling matrix of the box element
+ * (row 3 a + c, row major; nu the handle's), beta(x) = alpha (Emin + x^penal_beta (Emax - Emin)).
+ *   load:         rhs_n = rhs_base_n + sum_{e contains n} beta(x_e) (G theta_e)_n on the OWNED node planes (ghost planes are left
+ *                 as they are; supports not applied -- tp_elasticity_solve multiplies by N); rhs_base NULL = 0, rhs == rhs_base
+ *                 works in place.  A gather in one fixed order: the same bits on any number of slabs.
+ *   sensitivity:  dfdx_e += scale beta'(x_e) sum_l w_l (N V_l)_e^T G theta_e   (the partial derivative at fixed T).
+ *   adjoint rhs:  g_n = scale sum_{e contains n} beta(x_e) sum_{a,c} G[(a,c), b(e,n)] (N sum_l w_l V_l)_{a,c}: the transpose of the
+ *                 load, one scalar per OWNED node -- the right-hand side of the thermal adjoint.
+ * The supports N of the handle are applied inside; the ghost planes of T and of every distinct V_l are refreshed first.  With
+ * K u = N (F + f_th) and A(k) T = N_T q:  d(u^T K u)/dx = tp_elasticity_response's dfdx + the sensitivity with V = u, scale = 2,
+ * + tp_conduction_response's dfdx with T = [T], V = [mu], w = [2], where A mu = N_T g(u) (scale 1).  No call reduces anything
+ * or makes the host wait.
+ * TP_ERR_ARG unless every pointer but rhs_base and w is given, alpha and T_ref are finite, penal_beta >= 1, Emin >= 0,
+ * Emax > Emin, scale is finite and 1 <= ncase <= TP_MAX_CASES; TP_ERR_STATE before the supports are set. */
+typedef struct { double alpha, T_ref, Emin, Emax, penal_beta; } tp_thermal_par;
+int tp_elasticity_thermal_load(tp_elasticity *e, const double *xPhys /*[dev, own elements]*/, const double *T /*[dev, local nodes]*/,
+                            const tp_thermal_par *par, const double *rhs_base /*[dev, local nodes*3] or NULL*/, double *rhs /*[dev]*/);
+int tp_elasticity_thermal_sensitivity(tp_elasticity *e, int ncase, const double *const *V /*host array of [dev] pointers*/,
+                            const double *w /*host, NULL = all 1*/, const double *xPhys, const double *T,
+                            const tp_thermal_par *par, double scale, double *dfdx /*[dev, own elements], added to*/);
+int tp_elasticity_thermal_adjoint_rhs(tp_elasticity *e, int ncase, const double *const *V, const double *w, const double *xPhys,
+                            const tp_thermal_par *par, double scale, double *g /*[dev, local nodes], owned planes written*/);
+int tp_elasticity_get_thermal_coupling(const tp_elasticity *e, double *G_host_192);
+/* introspection for parity tests: beta(x_e) and beta'(x_e) of the own elements, as the three calls above form them; one of the
+ * two outputs may be NULL (the load and the adjoint rhs form beta alone, the sensitivity beta' alone) */
+int tp_elasticity_thermal_coefficients(tp_elasticity *e, const double *xPhys, const tp_thermal_par *par,
+                            double *beta /*[dev, own elements]*/, double *dbeta /*[dev, own elements]*/);
 /* The consistent mass matrix as an operator, and the mass half of an eigenvalue's design sensitivity (free vibration:
  * A phi = lambda B phi with A = N K N + (I - N), what tp_elasticity_apply applies, and B = N M N).
  *   M_e = rho0 m(x_e) V_e (M8 (x) I_3),  M8[a,b] = (1/8) prod_axis (2/3 if corners a, b share that coordinate, else 1/3)

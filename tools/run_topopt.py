@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """End-to-end run of the reference's optimisation loop on the MI355X path.
-usage: run_topopt.py [--physics elasticity|heat] [--loadcase top[:weight]]... [--stress-limit L [--stress-p P] [--stress-q q]] [--local-volume ALPHA:R] [--overhang +z|-z|+y|-y] [--self-weight bx,by,bz[:xlow] [--no-point-load]] [--length-scale both|solid|void[:C]] [--frequency-limit L[:nev]] [--passive solid|void:box|sphere|cylinder:numbers]... [--robust ETA_E,ETA_N,ETA_D[:every]] ex ey ez nlvls n_iter [filter [nsmooth ncoarse]]
+usage: run_topopt.py [--physics elasticity|heat|thermoelastic [--alpha A] [--thermal uniform:DT] [--t-ref T] [--thermal-penal P]] [--loadcase top[:weight]]... [--stress-limit L [--stress-p P] [--stress-q q]] [--local-volume ALPHA:R] [--overhang +z|-z|+y|-y] [--self-weight bx,by,bz[:xlow] [--no-point-load]] [--length-scale both|solid|void[:C]] [--frequency-limit L[:nev]] [--passive solid|void:box|sphere|cylinder:numbers]... [--robust ETA_E,ETA_N,ETA_D[:every]] ex ey ez nlvls n_iter [filter [nsmooth ncoarse]]
 (e.g. 128 128 128 5 20 1 2 45: the cycle of bench.py; --loadcase top:0.5 adds the line load on the upper edge as a second load
 case of weight 0.5 -- the objective becomes the weighted sum of the cases' compliances; --stress-limit L holds the von Mises
 p-norm of load case 0 below L as a second constraint, exponent --stress-p (8), stress relaxation x^q with --stress-q (0.5); --local-volume ALPHA:R holds the mean density in a ball of
@@ -19,7 +19,10 @@ DESIGN 4.16 with the Heaviside projection switched on: the compliance of the des
 dilated at 0.3 so that the nominal one at 0.5 meets volfrac, the dilated target recomputed every `every` (20) iterations;
 --physics heat runs the heat-sink problem of DESIGN 4.17 instead of the cantilever: steady conduction with a sink patch on the face
 x = 0 and a uniform source, conductivity 1e-3 + xPhys^3 (1 - 1e-3), the thermal compliance as the objective -- with --passive
-only, none of the other options)"""
+only, none of the other options; --physics thermoelastic --alpha A runs the cantilever under its point load plus the thermal
+expansion of a temperature field: by default the heat-sink problem's, solved on the same grid, with --thermal
+uniform:DT a uniform rise DT above the reference temperature --t-ref (0); --thermal-penal is the exponent of the thermal stress
+coefficient's interpolation (the stiffness's) -- with --passive only, none of the other options)"""
 import os
 import sys
 
@@ -112,13 +115,30 @@ if robust_arg is not None:
     except ValueError:
         sys.exit("--robust needs ETA_E,ETA_N,ETA_D[:every], e.g. 0.7,0.5,0.3:20, got %r" % robust_arg)
 physics = _last("--physics") or "elasticity"
-if physics not in ("elasticity", "heat"):
-    sys.exit("--physics needs elasticity or heat, got %r" % physics)
+if physics not in ("elasticity", "heat", "thermoelastic"):
+    sys.exit("--physics needs elasticity, heat or thermoelastic, got %r" % physics)
+thermo = {}
+alpha_arg, thermal_arg, tref_arg, tpenal_arg = _last("--alpha"), _last("--thermal"), _last("--t-ref"), _last("--thermal-penal")
+if physics == "thermoelastic":
+    if alpha_arg is None:
+        sys.exit("--physics thermoelastic needs --alpha A")
+    try:
+        thermo = dict(alpha=float(alpha_arg), T_ref=float(tref_arg) if tref_arg is not None else 0.0,
+                      thermal_penal=float(tpenal_arg) if tpenal_arg is not None else None)
+        if thermal_arg is not None:
+            kind, _, dt = thermal_arg.partition(":")
+            if kind != "uniform" or not dt:
+                raise ValueError(thermal_arg)
+            thermo.update(thermal="uniform", delta_T=float(dt))
+    except ValueError:
+        sys.exit("--alpha, --t-ref and --thermal-penal need numbers, --thermal needs uniform:DT; got %r, %r, %r, %r" % (alpha_arg, tref_arg, tpenal_arg, thermal_arg))
+elif any(v is not None for v in (alpha_arg, thermal_arg, tref_arg, tpenal_arg)):
+    sys.exit("--alpha, --thermal, --t-ref and --thermal-penal belong to --physics thermoelastic")
 ex, ey, ez, nlv, nit = [int(v) for v in sys.argv[1:6]]
 flt = int(sys.argv[6]) if len(sys.argv) > 6 else 1
 h = 1.0 / ey
 opt = tp.TopOpt(nxyz=(ex + 1, ey + 1, ez + 1), xc=(0, ex * h, 0, 1, 0, ez * h), nlvls=nlv, rmin=2.56 * h, filter=flt,
-                loadcases=loadcases or None, **stress, **local, overhang=overhang, **body, **length, **frequency, passive=shapes or None, **robust, physics=physics,
+                loadcases=loadcases or None, **stress, **local, overhang=overhang, **body, **length, **frequency, passive=shapes or None, **robust, physics=physics, **thermo,
                 solver=tp.SolverOptions(nlvls=nlv, **(dict(nsmooth=int(sys.argv[7]), ncoarse=int(sys.argv[8])) if len(sys.argv) > 8 else {})))
 print("# %dx%dx%d elements, %d DOF, %d MG levels, filter %d, rmin %.4f" % (ex, ey, ez, (1 if physics == "heat" else 3) * (ex + 1) * (ey + 1) * (ez + 1), nlv, flt, 2.56 * h))
 for it in range(nit):
@@ -131,6 +151,8 @@ for it in range(nit):
               % (r["stress_pnorm"], r["stress_max"], r["gx_stress"], r["ksp_its_adjoint"]), flush=True)
     if "print_loss" in r:
         print("Overhang:      build %s, mean(xPhys - xPrint): %f" % (overhang, r["print_loss"]), flush=True)
+    if "ksp_its_thermal" in r:
+        print("Thermoelastic: T max: %e | conduction iter: %d, thermal adjoint iter: %d" % (r["T_max"], r["ksp_its_thermal"], r["ksp_its_thermal_adjoint"]), flush=True)
     if "body_share" in r:
         print("Self-weight:   b: %s, x_low: %g, body load's share of the compliance: %f" % (",".join("%g" % v for v in opt.body_force), opt.body_force_xlow, r["body_share"]), flush=True)
     if "gx_solid" in r:

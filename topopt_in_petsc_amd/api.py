@@ -51,6 +51,23 @@ def check_body_force(b, x_low):
     return b, x_low
 
 
+def check_thermal(alpha, T_ref, penal_beta, Emin, Emax):
+    """-> (alpha, T_ref, Emin, Emax, penal_beta) as floats, the order of tp_thermal_par; ValueError unless alpha and T_ref are
+    finite, penal_beta >= 1 and 0 <= Emin < Emax"""
+    import math
+    try:
+        alpha, T_ref, penal_beta, Emin, Emax = (float(v) for v in (alpha, T_ref, penal_beta, Emin, Emax))
+    except (TypeError, ValueError):
+        raise ValueError("thermal expansion: need numbers, got %r" % ((alpha, T_ref, penal_beta, Emin, Emax),))
+    if not (math.isfinite(alpha) and math.isfinite(T_ref)):
+        raise ValueError("thermal expansion: alpha and T_ref must be finite, got %r, %r" % (alpha, T_ref))
+    if not (math.isfinite(penal_beta) and penal_beta >= 1.0):
+        raise ValueError("thermal expansion: the exponent must be at least 1, got %r" % (penal_beta,))
+    if not (math.isfinite(Emin) and math.isfinite(Emax) and 0.0 <= Emin < Emax):
+        raise ValueError("thermal expansion: need 0 <= Emin < Emax, both finite; got %r, %r" % (Emin, Emax))
+    return alpha, T_ref, Emin, Emax, penal_beta
+
+
 def _ptr(t):
     if t is None:
         return None
@@ -335,6 +352,8 @@ class LinearElasticity:
         self.adjoint_its, self.adjoint_rnorm, self.adjoint_bnorm = 0, 0.0, 0.0
         # self-weight (SetBodyForce): None = off; the total loads F_l + f(xPhys) live in buffers of their own, made on first use
         self.body_force, self.body_xlow, self._case_total = None, 0.1, []
+        # thermal expansion (SetThermalExpansion): None = off; the temperature field is the caller's (SetTemperature)
+        self.thermal, self._temperature = None, None
         # eigenmodes: the block of Ritz vectors persists like the states (warm start across design iterations); made by the
         # first Eigenmodes call
         self._eig = None
@@ -514,7 +533,77 @@ class LinearElasticity:
             self._case_total.append(self.grid.node_vec(3))
         for rhs, total in zip(self._case_rhs, self._case_total):
             total.copy_(rhs)   # (the ghost planes too)
-            self.BodyLoad(xPhys, total, base=total)
+            if self.body_force is not None:
+                self.BodyLoad(xPhys, total, base=total)
+            if self.thermal is not None:
+                self.ThermalLoad(xPhys, self._temperature_set(), total, base=total)
+
+    # ---- thermal expansion: a temperature field that loads the structure ----
+    def SetThermalExpansion(self, alpha, T_ref=0.0, penal_beta=None, Emin=1.0e-9, Emax=1.0):
+        """beta(x) = alpha (Emin + x^penal_beta (Emax - Emin)), the thermal stress coefficient per unit of T - T_ref
+        (include/topopt_amd.h; penal_beta None: 3).  From now on SolveState solves on F_l + f_th(xPhys, T) with T the field of
+        SetTemperature, and the sensitivities carry the load's term at fixed T.  alpha None switches it off again."""
+        if alpha is None:
+            self.thermal = None
+            if self.body_force is None:
+                self._case_total = []
+            return
+        self.thermal = check_thermal(alpha, T_ref, 3.0 if penal_beta is None else penal_beta, Emin, Emax)
+
+    def SetTemperature(self, T):
+        """the nodal temperature field (local node layout, one value per node) the thermal load is formed from; kept by
+        reference: the caller's solver writes it, SolveState reads it"""
+        self._temperature = T
+
+    def _temperature_set(self):
+        if self._temperature is None:
+            raise TopOptError(2, "thermal expansion (no temperature field: SetTemperature)")
+        return self._temperature
+
+    def _thermal_par(self):
+        if self.thermal is None:
+            raise TopOptError(2, "thermal expansion (not set: SetThermalExpansion)")
+        return C.byref(_lib.ThermalPar(*self.thermal))
+
+    def ThermalLoad(self, xPhys, T, out, base=None):
+        """out = base + f_th(xPhys, T) on the owned node planes (base None: f_th alone; out may be base); ghost planes stay"""
+        _chk(self.L.tp_elasticity_thermal_load(self.handle, _ptr(xPhys), _ptr(T), self._thermal_par(), _ptr(base), _ptr(out)),
+             "tp_elasticity_thermal_load")
+        return out
+
+    def ThermalSensitivity(self, V_list, w, xPhys, T, scale, dfdx):
+        """dfdx += scale * sum_l w_l d(v_l^T N f_th)/dxPhys at fixed T (w None: all weights 1); nothing is reduced"""
+        n = len(V_list)
+        Va = (C.c_void_p * max(n, 1))(*[_ptr(v) for v in V_list])
+        wa = None if w is None else (C.c_double * max(n, 1))(*[float(v) for v in w])
+        _chk(self.L.tp_elasticity_thermal_sensitivity(self.handle, n, Va, wa, _ptr(xPhys), _ptr(T), self._thermal_par(), float(scale),
+                                                      _ptr(dfdx)), "tp_elasticity_thermal_sensitivity")
+
+    def ThermalAdjointRHS(self, V_list, w, xPhys, scale, out):
+        """out = scale * sum_l w_l (d f_th / dT)^T N v_l on the owned node planes, one value per node: the right-hand side of the
+        thermal adjoint; ghost planes stay"""
+        n = len(V_list)
+        Va = (C.c_void_p * max(n, 1))(*[_ptr(v) for v in V_list])
+        wa = None if w is None else (C.c_double * max(n, 1))(*[float(v) for v in w])
+        _chk(self.L.tp_elasticity_thermal_adjoint_rhs(self.handle, n, Va, wa, _ptr(xPhys), self._thermal_par(), float(scale), _ptr(out)),
+             "tp_elasticity_thermal_adjoint_rhs")
+        return out
+
+    def ThermalCoefficients(self, xPhys, beta=None, dbeta=None):
+        """-> (beta, beta') per own element as the thermal passes form them (parity tests); with one of the two outputs given the
+        other is not formed and comes back as None"""
+        if beta is None and dbeta is None:
+            beta, dbeta = self.grid.elem_vec(), self.grid.elem_vec()
+        _chk(self.L.tp_elasticity_thermal_coefficients(self.handle, _ptr(xPhys), self._thermal_par(), _ptr(beta), _ptr(dbeta)),
+             "tp_elasticity_thermal_coefficients")
+        return beta, dbeta
+
+    def ThermalCoupling(self):
+        """the coupling matrix G of the element (24 x 8 row-major, numpy array of 192): f_e = beta G (T_e - T_ref)"""
+        import numpy as np
+        g = np.zeros(192)
+        _chk(self.L.tp_elasticity_get_thermal_coupling(self.handle, g.ctypes.data), "tp_elasticity_get_thermal_coupling")
+        return g
 
     # ---- free vibration: A phi = lambda B phi, A = N K N + (I - N) of the last assembly, B = N M N ----
     def MassAssemble(self, xPhys, rho0=1.0, x_low=0.1):
@@ -676,10 +765,11 @@ class LinearElasticity:
     def SolveState(self, xPhys, Emin, Emax, penal, hist_cap=0):
         """LinearElasticity.cc:182-223; several load cases: one assembly, then every case in index order"""
         self.AssembleStiffnessMatrix(xPhys, Emin, Emax, penal)
-        if self.body_force is not None:
+        loaded = self.body_force is not None or self.thermal is not None
+        if loaded:
             self._form_totals(xPhys)
         for case in range(self.ncases):
-            its = self.KSPSolve(hist_cap, case, rhs=self._case_total[case] if self.body_force is not None else None)
+            its = self.KSPSolve(hist_cap, case, rhs=self._case_total[case] if loaded else None)
         return its
 
     def Response(self, U_list, V_list, w, xPhys, Emin, Emax, penal, volfrac, dfdx=None, dgdx=None, sums=True):
@@ -771,6 +861,8 @@ class LinearElasticity:
         fx, gx = self._evaluate(dfdx, dgdx, True, xPhys, Emin, Emax, penal, volfrac)
         if self.body_force is not None:   # u^T K u = (F + f)^T u as it stands; dfdx gains 2 d(u^T N f)/dx per case
             self.BodySensitivity(self._case_U, self.case_weight, xPhys, 2.0, dfdx)
+        if self.thermal is not None:      # the same at fixed T; what T's own dependence on the design adds is the caller's
+            self.ThermalSensitivity(self._case_U, self.case_weight, xPhys, self._temperature_set(), 2.0, dfdx)
         return fx, gx
 
     def ComputeObjectiveConstraints(self, xPhys, Emin, Emax, penal, volfrac, hist_cap=0):
@@ -783,6 +875,8 @@ class LinearElasticity:
         self._evaluate(dfdx, dgdx, False, xPhys, Emin, Emax, penal, volfrac)
         if self.body_force is not None:
             self.BodySensitivity(self._case_U, self.case_weight, xPhys, 2.0, dfdx)
+        if self.thermal is not None:
+            self.ThermalSensitivity(self._case_U, self.case_weight, xPhys, self._temperature_set(), 2.0, dfdx)
 
     # ---- introspection used by the parity tests ----------------------------
     def petsc_options(self):
@@ -1002,6 +1096,15 @@ class HeatConduction:
     def SolveState(self, xPhys, kmin, kmax, penal, hist_cap=0):
         self.AssembleConductivityMatrix(xPhys, kmin, kmax, penal)
         return self.KSPSolve(hist_cap)
+
+    def SolveAdjoint(self, rhs, mu):
+        """A mu = N rhs on the last assembly, warm-started from mu (the caller's, as rhs) -> iterations.  The figures go to
+        adjoint_its / adjoint_rnorm / adjoint_bnorm; last_its and the records of the state solve stay as they are."""
+        its, rn, bn = C.c_int(), C.c_double(), C.c_double()
+        rc = self.L.tp_conduction_solve(self.handle, _ptr(rhs), _ptr(mu), C.byref(its), C.byref(rn), C.byref(bn), None, 0)
+        self.adjoint_its, self.adjoint_rnorm, self.adjoint_bnorm = its.value, rn.value, bn.value
+        _chk(rc, "tp_conduction_solve (adjoint)")
+        return its.value
 
     def Response(self, T_list, V_list, w, xPhys, kmin, kmax, penal, volfrac, dfdx=None, dgdx=None, sums=True):
         """tp_conduction_response: fx = sum_l w_l f_l with f_l = sum_e k_e v_l^T KT t_l, gx, dfdx, dgdx for all cases in one pass

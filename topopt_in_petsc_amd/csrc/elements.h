@@ -171,3 +171,29 @@ inline void conduction_element_box(double dx, double dy, double dz, double *KT /
     if (v8)
         for (int q = 0; q < 8; q++) v8[q] = v[q];
 }
+
+// Thermoelastic coupling matrix G[(a,c), b] = 1 / (1 - 2 nu) int dN_a/dx_c N_b dV on a box element (24 x 8, row 3 a + c, row
+// major): B^T D0 phi N_b integrated, D0 the unit-modulus isotropic matrix, phi = (1, 1, 1, 0, 0, 0).  A tensor product: along
+// axis c the factor int dN_a/dx N_b = -+ 1/2 (the sign is corner a's side of the axis), along the two other axes the 1-D mass
+// M_d = h_d [[2, 1], [1, 2]] / 6.  Nine magnitudes, g9[3 c + m] with m the number of the two other axes along which a and b
+// differ (weights 4, 2, 1 of h_d1 h_d2 / 36) -- optional, what the kernels take as arguments.
+inline void thermal_coupling_box(double dx, double dy, double dz, double nu, double *G /*192*/, double *g9 = nullptr) {
+    const double h[3] = {dx, dy, dz};
+    const double pre = 0.5 / (1.0 - 2.0 * nu);
+    double m9[9];
+    for (int c = 0; c < 3; c++) {
+        const double area = h[(c + 1) % 3] * h[(c + 2) % 3];
+        m9[3 * c + 0] = pre * (area / 9.0);
+        m9[3 * c + 1] = pre * (area / 18.0);
+        m9[3 * c + 2] = pre * (area / 36.0);
+    }
+    const int l[3][8] = {{0, 1, 1, 0, 0, 1, 1, 0}, {0, 0, 1, 1, 0, 0, 1, 1}, {0, 0, 0, 0, 1, 1, 1, 1}};
+    for (int a = 0; a < 8; a++)
+        for (int c = 0; c < 3; c++)
+            for (int b = 0; b < 8; b++) {
+                const int m = (l[(c + 1) % 3][a] != l[(c + 1) % 3][b]) + (l[(c + 2) % 3][a] != l[(c + 2) % 3][b]);
+                G[(3 * a + c) * 8 + b] = l[c][a] ? m9[3 * c + m] : -m9[3 * c + m];
+            }
+    if (g9)
+        for (int q = 0; q < 9; q++) g9[q] = m9[q];
+}

@@ -527,6 +527,8 @@ struct tp_elasticity {
     DevBuf<double> d_resp;       // block partials of tp_elasticity_response, (TP_MAX_CASES + 1) x resp_nb, allocated by its first sums
     long resp_nb = 0;
     DevBuf<double> d_xg;         // tp_elasticity_body_load: the upper neighbour's first own layer of xPhys (slabs, first use)
+    double G[192], G9[9];        // thermoelastic coupling matrix of the element and its nine magnitudes (elements.h), from h and opts.nu
+    DevBuf<double> d_beta, d_dbeta;  // tp_elasticity_thermal_*: beta(x_e), beta'(x_e), own + ghost-above layer (first use)
     bool have_bc = false, assembled = false;
     DevBuf<double> d_mc;         // tp_elasticity_mass_assemble: rho0 V_e m(x_e), own + ghost-above layer (first use)
     double mass_rv = 0.0, mass_xlow = 0.0, mass_invlow = 0.0;   // ... and rho0 V_e, x_low, 1 / x_low of that call
@@ -606,6 +608,7 @@ extern "C" int tp_elasticity_create_ke(tp_elasticity **out, tp_grid *g, const tp
     if (ke_host_576) std::memcpy(e->KE, ke_host_576, sizeof(e->KE));
     else hex8_stiffness_box(g->o.hx, g->o.hy, g->o.hz, o->nu, e->KE);
     hex8_vonmises_form_box(g->o.hx, g->o.hy, g->o.hz, o->nu, e->VM);
+    thermal_coupling_box(g->o.hx, g->o.hy, g->o.hz, o->nu, e->G, e->G9);
     std::vector<double> M(8 * 576);
     host_child_matrices(e->KE, M.data());
     TP_TRY(e->mg.alloc_levels());
@@ -1386,12 +1389,13 @@ extern "C" int tp_elasticity_last_op_form(const tp_elasticity *e, int *form4) {
 }
 
 // ===========================================================================
-// responses of the state: compliance of one or several load cases, von Mises stress p-norm, self-weight, the mass operator and
+// responses of the state: compliance of one or several load cases, von Mises stress p-norm, self-weight, thermal expansion, the mass operator and
 // the block-vector passes of the eigen-solver
 // ===========================================================================
 #include "response.h"
 #include "stress.h"
 #include "bodyforce.h"
+#include "thermoelastic.h"
 #include "mass.h"
 #include "blockvec.h"
 

@@ -16,7 +16,7 @@ import torch
 from . import mpiio
 import ctypes as C
 
-from .api import Filter, Grid, HeatConduction, LengthScale, LinearElasticity, LocalVolume, MMA, Overhang, Passive, Robust, SolverOptions, _chk, _ptr, check_body_force, passive_labels
+from .api import Filter, Grid, HeatConduction, LengthScale, LinearElasticity, LocalVolume, MMA, Overhang, Passive, Robust, SolverOptions, _chk, _ptr, check_body_force, check_thermal, passive_labels
 
 
 def robust_volume_target(volfrac, S_d, S_n):
@@ -139,14 +139,29 @@ class TopOpt:
     physics: str = "elasticity"
     kmin: float = 1.0e-3
     kmax: float = 1.0
+    # physics="thermoelastic" (DESIGN 4.18): the cantilever under its point load plus the thermal expansion of a temperature field,
+    # beta(x) = alpha (Emin + x^thermal_penal (Emax - Emin)) per unit of T - T_ref (thermal_penal None: penal).  thermal=
+    # "conduction": T is solved on the same grid from the heat-sink problem of physics="heat" (kmin, kmax as there) and the
+    # sensitivity carries the thermal adjoint; "uniform": T = T_ref + delta_T everywhere, no conduction solve.  After
+    # construction `thermal` is the HeatConduction object or None, `thermal_kind` keeps the name
+    alpha: float = None
+    T_ref: float = 0.0
+    thermal_penal: float = None
+    thermal: str = "conduction"
+    delta_T: float = None
     history: list = field(default_factory=list)
 
     def __post_init__(self):
         self.physics_kind = self.physics
-        if self.physics_kind not in ("elasticity", "heat"):
-            raise ValueError("physics must be 'elasticity' or 'heat', got %r" % (self.physics,))
+        if self.physics_kind not in ("elasticity", "heat", "thermoelastic"):
+            raise ValueError("physics must be 'elasticity', 'heat' or 'thermoelastic', got %r" % (self.physics,))
         if self.physics_kind == "heat":
             self._check_heat()
+        self.thermal_kind = self.thermal
+        if self.physics_kind == "thermoelastic":
+            self._check_thermoelastic()
+        elif self.alpha is not None or self.delta_T is not None:
+            raise ValueError("alpha and delta_T belong to physics='thermoelastic', got physics=%r" % (self.physics,))
         if self.robust is not None:
             self._check_robust()
         if self.overhang is not None and self.overhang not in Overhang.BUILDS:
@@ -213,6 +228,10 @@ class TopOpt:
         so = self.solver or SolverOptions(nlvls=self.nlvls, nu=self.nu)
         self.physics = (HeatConduction if self.physics_kind == "heat" else LinearElasticity)(self.grid, so)
         self.physics.SetUpLoadAndBC()
+        if self.physics_kind == "thermoelastic":
+            self._setup_thermoelastic(so)
+        else:
+            self.thermal = None
         # the material interpolation's end values as the physics takes them
         self._dof = 1 if self.physics_kind == "heat" else 3
         self._mat = (self.kmin, self.kmax) if self.physics_kind == "heat" else (self.Emin, self.Emax)
@@ -299,6 +318,77 @@ class TopOpt:
             raise ValueError("physics='heat' needs 0 < kmin < kmax, both finite; got %r, %r" % (self.kmin, self.kmax))
         if not (math.isfinite(self.penal) and self.penal >= 1.0):
             raise ValueError("physics='heat' needs penal >= 1, got %r" % (self.penal,))
+
+    def _check_thermoelastic(self):
+        """the thermoelastic problem's refusals; host arithmetic on the parameters, before any device object"""
+        import math
+        for name, what in (("loadcases", "further load cases"), ("stress_limit", "the stress constraint"), ("body_force", "self-weight"),
+                           ("frequency_limit", "the eigenfrequency constraint"), ("robust", "robust design"), ("overhang", "the overhang filter"),
+                           ("local_volume", "the local volume constraint"), ("length_scale", "the length-scale constraints")):
+            if getattr(self, name) is not None:
+                raise ValueError("physics='thermoelastic' together with %s (%s) is not supported" % (name, what))
+        if self.alpha is None:
+            raise ValueError("physics='thermoelastic' needs alpha, the thermal stress coefficient at Emax per unit of temperature")
+        if self.thermal_kind not in ("conduction", "uniform"):
+            raise ValueError("thermal must be 'conduction' or 'uniform', got %r" % (self.thermal_kind,))
+        if self.thermal_kind == "uniform":
+            if self.delta_T is None or not math.isfinite(float(self.delta_T)):
+                raise ValueError("thermal='uniform' needs a finite delta_T, the temperature rise above T_ref")
+            self.delta_T = float(self.delta_T)
+        else:
+            if self.delta_T is not None:
+                raise ValueError("delta_T belongs to thermal='uniform': with thermal='conduction' the temperature is solved for")
+            if not (math.isfinite(self.kmin) and math.isfinite(self.kmax) and self.kmin > 0.0 and self.kmax > self.kmin):
+                raise ValueError("thermal='conduction' needs 0 < kmin < kmax, both finite; got %r, %r" % (self.kmin, self.kmax))
+        if not (math.isfinite(self.penal) and self.penal >= 1.0):
+            raise ValueError("physics='thermoelastic' needs penal >= 1, got %r" % (self.penal,))
+        self._thermal_par = check_thermal(self.alpha, self.T_ref, self.penal if self.thermal_penal is None else self.thermal_penal,
+                                          self.Emin, self.Emax)
+
+    def _setup_thermoelastic(self, so):
+        """the second state problem on the SAME grid, the temperature field the elastic load reads, the thermal adjoint's vectors"""
+        g, ph = self.grid, self.physics
+        alpha, T_ref, Emin, Emax, pb = self._thermal_par
+        ph.SetThermalExpansion(alpha, T_ref, pb, Emin, Emax)
+        if self.thermal_kind == "conduction":
+            self.thermal = HeatConduction(g, so)
+            self.thermal.SetUpLoadAndBC()
+            ph.SetTemperature(self.thermal.T)
+            # mu persists like the states (warm start across design iterations); the ghost planes of its load stay 0
+            self.mu, self._g_th, self._df_th = g.node_vec(1), g.node_vec(1), g.elem_vec()
+        else:
+            self.thermal = None
+            self._T_uniform = g.node_vec(1)
+            self._T_uniform.fill_(T_ref + self.delta_T)
+            ph.SetTemperature(self._T_uniform)
+
+    def _thermoelastic_step(self):
+        """conduction solve -> thermal load and elastic solve -> compliance and its sensitivity at fixed T (the load's term with
+        factor 2 inside) -> the thermal adjoint's right-hand side, its solve and the conduction response with weight 2 -> (fx, gx)"""
+        ph, th, x = self.physics, self.thermal, self.xPrint
+        self._its_thermal = self._its_thermal_adjoint = 0
+        if th is not None:
+            self._its_thermal = th.SolveState(x, self.kmin, self.kmax, self.penal)
+        fx, gx = ph.ComputeObjectiveConstraintsSensitivities(self.dfdx, self.dgdx[0], x, self.Emin, self.Emax, self.penal, self.volfrac)
+        if th is not None:
+            ph.ThermalAdjointRHS([ph.U], None, x, 1.0, self._g_th)
+            self._its_thermal_adjoint = th.SolveAdjoint(self._g_th, self.mu)
+            # (tp_conduction_response overwrites its dfdx: through a scratch vector)
+            th.Response([th.T], [self.mu], [2.0], x, self.kmin, self.kmax, self.penal, 0.0, dfdx=self._df_th, sums=False)
+            self.dfdx.add_(self._df_th)
+        return fx, gx
+
+    def _T_max(self):
+        """the largest temperature of the field the load was formed from, all ranks"""
+        if self.thermal is None:
+            return self.T_ref + self.delta_T
+        m = float(self.thermal.T[self.grid.part.owned_slice(1)].max())
+        if self.nranks == 1:
+            return m
+        import torch.distributed as dist
+        parts = [None] * self.nranks
+        dist.all_gather_object(parts, m)
+        return max(parts)
 
     def _check_robust(self):
         """robust mode's refusals; host arithmetic on the parameters, before any device object"""
@@ -419,9 +509,12 @@ class TopOpt:
         """one pass of the loop body, main.cc:54-111; returns the record of this iteration"""
         self.itr += 1
         t1 = time.perf_counter()
-        fx, gx = self.physics.ComputeObjectiveConstraintsSensitivities(
-            self.dfdx, self.dgdx[0], self.xPrint if self.robust is None else self.xErode, self._mat[0], self._mat[1], self.penal,
-            self.volfrac)                                                                        # main.cc:62
+        if self.physics_kind == "thermoelastic":
+            fx, gx = self._thermoelastic_step()
+        else:
+            fx, gx = self.physics.ComputeObjectiveConstraintsSensitivities(
+                self.dfdx, self.dgdx[0], self.xPrint if self.robust is None else self.xErode, self._mat[0], self._mat[1], self.penal,
+                self.volfrac)                                                                    # main.cc:62
         if self.robust is not None:   # the volume on the dilated design, against V_d*
             S, n_glob = list(self._S), self.grid.part.n_own_elems * self.nranks
             if robust_volume_due(self.itr, self.robust_volume_every):
@@ -432,6 +525,8 @@ class TopOpt:
                 f_real = self._solve_realisations(fx)
         if self.body_force is not None:   # (before xPrint moves on)
             body_share = self._body_share()
+        if self.physics_kind == "thermoelastic":
+            T_max = self._T_max()
         if self.itr == 1:
             self.fscale = 10.0 / fx                                                              # :68-70
         fxs = fx * self.fscale
@@ -518,6 +613,8 @@ class TopOpt:
             rec["print_loss"] = self._mean(self.xPhys - self.xPrint)
         if self.body_force is not None:
             rec["body_share"] = body_share
+        if self.physics_kind == "thermoelastic":
+            rec["ksp_its_thermal"], rec["ksp_its_thermal_adjoint"], rec["T_max"] = self._its_thermal, self._its_thermal_adjoint, T_max
         if self.regions is not None:
             rec["n_active"] = self.n_active
         if self.robust is not None:   # of the design fx and gx belong to

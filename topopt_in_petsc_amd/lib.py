@@ -37,6 +37,11 @@ class SolverOpts(C.Structure):
                 ("coarse_restart", C.c_int), ("coarse_rtol", C.c_double), ("coarse_direct", C.c_int)]
 
 
+class ThermalPar(C.Structure):
+    """tp_thermal_par"""
+    _fields_ = [("alpha", C.c_double), ("T_ref", C.c_double), ("Emin", C.c_double), ("Emax", C.c_double), ("penal_beta", C.c_double)]
+
+
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_long)
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int)
 DIRECT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long)
@@ -111,6 +116,11 @@ SYMBOLS = {
     "tp_elasticity_get_stress_form": (_i, [_vp, _vp]),
     "tp_elasticity_body_load": (_i, [_vp, _vp, C.POINTER(_d), _d, _vp, _vp]),
     "tp_elasticity_body_sensitivity": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_d), _vp, C.POINTER(_d), _d, _d, _vp]),
+    "tp_elasticity_thermal_load": (_i, [_vp, _vp, _vp, C.POINTER(ThermalPar), _vp, _vp]),
+    "tp_elasticity_thermal_sensitivity": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_d), _vp, _vp, C.POINTER(ThermalPar), _d, _vp]),
+    "tp_elasticity_thermal_adjoint_rhs": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_d), _vp, C.POINTER(ThermalPar), _d, _vp]),
+    "tp_elasticity_get_thermal_coupling": (_i, [_vp, _vp]),
+    "tp_elasticity_thermal_coefficients": (_i, [_vp, _vp, C.POINTER(ThermalPar), _vp, _vp]),
     "tp_elasticity_mass_assemble": (_i, [_vp, _vp, _d, _d]),
     "tp_elasticity_mass_apply": (_i, [_vp, _vp, _vp]),
     "tp_elasticity_mass_sensitivity": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_d), _vp, _d, _vp]),
