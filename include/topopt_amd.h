@@ -369,6 +369,33 @@ int tp_elasticity_mass_apply(tp_elasticity *e, const double *u /*[dev, local nod
 int tp_elasticity_mass_sensitivity(tp_elasticity *e, int ncase, const double *const *V /*host array of [dev] pointers*/,
                             const double *w /*host, NULL = all 1*/, const double *xPhys, double scale,
                             double *out /*[dev, own elements], added to*/);
+/* The geometric (stress) stiffness as an operator and its two derivatives: the pieces of a linear buckling analysis
+ * B phi = mu A phi with B = -N G(x, u) N, A as above, u the state of one load case (load factors 1 / mu of the positive mu).
+ *   sigma(gp) = C0 B(gp) u_e at the 8 Gauss points of the element (2 x 2 x 2 rule, weight hx hy hz / 8, C0 the unit-modulus
+ *   isotropic matrix),  g_e[a,b] = sum_gp w gradN_a(gp)^T S(sigma(gp)) gradN_b(gp)  (8 x 8, symmetric, rows sum to zero),
+ *   G_e = Emax x_e^penal (g_e (x) I_3)  -- no Emin: a void element carries no stress stiffness.
+ *   geom_assemble:    Emax x_e^penal g_e(u_e) of the own elements and the ghost layer above (28 entries a < b), once per design
+ *                     and state; the ghost planes of U are refreshed inside
+ *   geom_apply:       y = N G N phi on the OWNED node planes (the ghost planes of phi are refreshed inside, those of y are left
+ *                     as they are; phi != y).  A gather in one fixed order: the same bits on any number of slabs.
+ *   geom_sensitivity: out_e += scale penal x_e^(penal-1) Emax sum_l w_l (N Phi_l)_e^T (g_e(U_e) (x) I_3) (N Phi_l)_e  (w NULL = all
+ *                     1; ghost planes of every distinct Phi_l and of U refreshed first).  No reduction, the host does not wait.
+ *   geom_adjoint_rhs: out = scale sum_l w_l d((N Phi_l)^T G (N Phi_l)) / dU on the OWNED node planes, supports not applied
+ *                     (tp_elasticity_solve multiplies by N); ghost planes of out stay.  A gather in one fixed order.
+ * TP_ERR_ARG, before the grid is touched, unless every pointer is given, Emax > 0, penal >= 1 and scale are finite and
+ * 1 <= ncase <= TP_MAX_CASES; TP_ERR_ARG for the last three before a geom_assemble; TP_ERR_STATE for geom_assemble before
+ * the supports are set. */
+int tp_elasticity_geom_assemble(tp_elasticity *e, const double *xPhys /*[dev, own elements]*/, const double *U /*[dev, local nodes*3]*/,
+                            double Emax, double penal);
+int tp_elasticity_geom_apply(tp_elasticity *e, const double *phi /*[dev, local nodes*3]*/, double *y /*[dev, local nodes*3]*/);
+int tp_elasticity_geom_sensitivity(tp_elasticity *e, int ncase, const double *const *Phi /*host array of [dev] pointers*/,
+                            const double *w /*host, NULL = all 1*/, const double *xPhys, const double *U, double Emax, double penal,
+                            double scale, double *out /*[dev, own elements], added to*/);
+int tp_elasticity_geom_adjoint_rhs(tp_elasticity *e, int ncase, const double *const *Phi /*host array of [dev] pointers*/,
+                            const double *w /*host, NULL = all 1*/, const double *xPhys, double Emax, double penal, double scale,
+                            double *out /*[dev, local nodes*3]*/);
+/* the element's tables for the parity tests: gradN[(3 gp + d) * 8 + n] = dN_n/dx_d, cb[(6 gp + r) * 24 + j] = (C0 B(gp))[r][j] */
+int tp_elasticity_get_geom_tables(const tp_elasticity *e, double *gradN_host_192, double *cb_host_1152);
 /* introspection for parity tests */
 /* KSPSetTolerances (LinearElasticity.cc:646); a negative value keeps the current one (PETSC_DEFAULT) */
 int tp_elasticity_set_tolerances(tp_elasticity *le, double rtol, double atol, double dtol, int max_it);

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """End-to-end run of the reference's optimisation loop on the MI355X path.
-usage: run_topopt.py [--physics elasticity|heat|thermoelastic [--alpha A] [--thermal uniform:DT] [--t-ref T] [--thermal-penal P]] [--loadcase top[:weight]]... [--stress-limit L [--stress-p P] [--stress-q q]] [--local-volume ALPHA:R] [--overhang +z|-z|+y|-y] [--self-weight bx,by,bz[:xlow] [--no-point-load]] [--length-scale both|solid|void[:C]] [--frequency-limit L[:nev]] [--passive solid|void:box|sphere|cylinder:numbers]... [--robust ETA_E,ETA_N,ETA_D[:every]] ex ey ez nlvls n_iter [filter [nsmooth ncoarse]]
+usage: run_topopt.py [--physics elasticity|heat|thermoelastic [--alpha A] [--thermal uniform:DT] [--t-ref T] [--thermal-penal P]] [--loadcase top[:weight]]... [--stress-limit L [--stress-p P] [--stress-q q]] [--local-volume ALPHA:R] [--overhang +z|-z|+y|-y] [--self-weight bx,by,bz[:xlow] [--no-point-load]] [--length-scale both|solid|void[:C]] [--frequency-limit L[:nev]] [--load cantilever|axial] [--buckling-limit L[:nev]] [--passive solid|void:box|sphere|cylinder:numbers]... [--robust ETA_E,ETA_N,ETA_D[:every]] ex ey ez nlvls n_iter [filter [nsmooth ncoarse]]
 (e.g. 128 128 128 5 20 1 2 45: the cycle of bench.py; --loadcase top:0.5 adds the line load on the upper edge as a second load
 case of weight 0.5 -- the objective becomes the weighted sum of the cases' compliances; --stress-limit L holds the von Mises
 p-norm of load case 0 below L as a second constraint, exponent --stress-p (8), stress relaxation x^q with --stress-q (0.5); --local-volume ALPHA:R holds the mean density in a ball of
@@ -11,6 +11,9 @@ density) that moves with the design, the mass of elements below xlow (0.1) dampe
 load; --length-scale KINDS[:C] holds a minimum length scale of the solid and / or the void phase by the geometric constraints of
 DESIGN 4.13 as the last constraints, decay C in length^2 (default rmin^4 / h^2), with the Heaviside projection switched on;
 --frequency-limit L[:nev] holds the harmonic mean of the lowest nev (3) eigenvalues of K phi = lambda M phi above L, DESIGN 4.14;
+--load axial replaces the reference's line load by a uniform traction along -x on the face x = xmax, total 1 (a column in
+compression); --buckling-limit L[:nev] holds the lowest linear buckling load factor of load case 0 above L through the p-norm of
+the nev (2) largest eigenvalues of -G phi = mu K phi, DESIGN 4.19 -- best together with --load axial;
 --passive KIND:SHAPE:numbers holds the elements whose centres lie in a shape at full density (solid) or empty (void), the passive
 regions of DESIGN 4.15, in physical coordinates (the box is ex/ey x 1 x ez/ey): box:x0,x1,y0,y1,z0,z1, sphere:cx,cy,cz,r or
 cylinder:axis,c1,c2,r (axis x, y or z, infinite along it); later shapes override earlier ones, e.g.
@@ -98,6 +101,16 @@ if frequency_limit is not None:
         frequency = dict(frequency_limit=float(lim), frequency_modes=int(nev) if nev else 3)
     except ValueError:
         sys.exit("--frequency-limit needs L[:nev], got %r" % frequency_limit)
+load_arg = _last("--load") or "cantilever"
+if load_arg not in ("cantilever", "axial"):
+    sys.exit("--load needs cantilever or axial, got %r" % load_arg)
+buckling_limit, buckling = _last("--buckling-limit"), {}
+if buckling_limit is not None:
+    lim, _, nev = buckling_limit.partition(":")
+    try:
+        buckling = dict(buckling_limit=float(lim), buckling_modes=int(nev) if nev else 2)
+    except ValueError:
+        sys.exit("--buckling-limit needs L[:nev], got %r" % buckling_limit)
 shapes = []
 for v in _option("--passive", ": solid|void:box|sphere|cylinder:numbers"):
     try:
@@ -138,7 +151,7 @@ ex, ey, ez, nlv, nit = [int(v) for v in sys.argv[1:6]]
 flt = int(sys.argv[6]) if len(sys.argv) > 6 else 1
 h = 1.0 / ey
 opt = tp.TopOpt(nxyz=(ex + 1, ey + 1, ez + 1), xc=(0, ex * h, 0, 1, 0, ez * h), nlvls=nlv, rmin=2.56 * h, filter=flt,
-                loadcases=loadcases or None, **stress, **local, overhang=overhang, **body, **length, **frequency, passive=shapes or None, **robust, physics=physics, **thermo,
+                loadcases=loadcases or None, **stress, **local, overhang=overhang, **body, **length, **frequency, load=load_arg, **buckling, passive=shapes or None, **robust, physics=physics, **thermo,
                 solver=tp.SolverOptions(nlvls=nlv, **(dict(nsmooth=int(sys.argv[7]), ncoarse=int(sys.argv[8])) if len(sys.argv) > 8 else {})))
 print("# %dx%dx%d elements, %d DOF, %d MG levels, filter %d, rmin %.4f" % (ex, ey, ez, (1 if physics == "heat" else 3) * (ex + 1) * (ey + 1) * (ez + 1), nlv, flt, 2.56 * h))
 for it in range(nit):
@@ -162,6 +175,10 @@ for it in range(nit):
     if "gx_frequency" in r:
         print("Frequency:     lambda: %s, gap: %f, gx[%d]: %f | subspace iter: %d, solver iter: %d"
               % (" ".join("%e" % v for v in r["eig"]), r["eig_gap"], opt._k_freq, r["gx_frequency"], r["eig_iters"], r["ksp_its_eigen"]), flush=True)
+    if "gx_buckling" in r:
+        print("Buckling:      mu: %s, load factor: %e, gap: %f, gx[%d]: %f | subspace iter: %d, solver iter: %d"
+              % (" ".join("%e" % v for v in r["buckling_mu"]), r["buckling_factor"], r["buckling_gap"], opt._k_buck, r["gx_buckling"],
+                 r["buckling_iters"], r["ksp_its_buckling"]), flush=True)
     if "n_active" in r:
         lab = opt.labels_own
         xp = opt.xPhys.cpu().numpy()

@@ -357,6 +357,8 @@ class LinearElasticity:
         # eigenmodes: the block of Ritz vectors persists like the states (warm start across design iterations); made by the
         # first Eigenmodes call
         self._eig = None
+        # buckling modes: the same for BucklingModes; the adjoint state of BucklingSensitivity persists too
+        self._buck = self._buck_adj = self._buck_rhs = self._buck_row = None
 
     def close(self):
         if getattr(self, "handle", None):
@@ -739,6 +741,193 @@ class LinearElasticity:
         self.Response(Phi, None, [1.0 / (l * l) for l in lam], xPhys, Emin, Emax, penal, 0.0, dfdx=out, sums=False)
         self.MassSensitivity(Phi, [1.0 / l for l in lam], xPhys, 1.0, out)
         return sum(1.0 / l for l in lam)
+
+    # ---- linear buckling: B phi = mu A phi, A as above, B = -N G(x, u) N the stress stiffness of a state u ----
+    def SetUpLoadAndBC_Axial(self, total=1.0):
+        """The cantilever's clamp (face x = xmin) under a uniform traction along -x on the face x = xmax, `total` in sum:
+        consistent nodal loads, total / (ey ez) / 4 from every face element to each of its four nodes.  A column in
+        compression: the load a buckling analysis starts from.  Single rank or z-slabs (global z index decides)."""
+        self.SetUpLoadAndBC()   # the supports
+        self.SetBC(self.N, self.AxialLoad(total))
+
+    def AxialLoad(self, total=1.0):
+        """the right-hand side of SetUpLoadAndBC_Axial in the local node layout (for AddLoadCase too)"""
+        p = self.grid.part
+        nx, ny, nzl = p.nx, p.ny, p.nz_local
+        R = torch.zeros(nzl, ny, nx, 3, dtype=torch.float64)
+        per = float(total) / ((ny - 1) * (p.nz - 1)) / 4.0
+        kz = torch.arange(nzl) + p.node_z0
+        wz = torch.where((kz == 0) | (kz == p.nz - 1), 1.0, 2.0).to(torch.float64)
+        wy = torch.full((ny,), 2.0, dtype=torch.float64)
+        wy[0] = wy[ny - 1] = 1.0
+        R[:, :, nx - 1, 0] = -per * wz[:, None] * wy[None, :]
+        return R.reshape(-1).to(self.U.device)
+
+    def GeomAssemble(self, xPhys, Emax, penal, U=None):
+        """Emax x^penal g_e(U_e) for GeomMult, once per design and state (U None: case 0's state)"""
+        _chk(self.L.tp_elasticity_geom_assemble(self.handle, _ptr(xPhys), _ptr(self.U if U is None else U), float(Emax), float(penal)),
+             "tp_elasticity_geom_assemble")
+
+    def GeomMult(self, phi, y=None):
+        """y = N G N phi on the owned node planes (ghost planes of y stay as they are)"""
+        y = torch.zeros_like(phi) if y is None else y
+        _chk(self.L.tp_elasticity_geom_apply(self.handle, _ptr(phi), _ptr(y)), "tp_elasticity_geom_apply")
+        return y
+
+    def GeomSensitivity(self, Phi_list, w, xPhys, U, Emax, penal, scale, out):
+        """out += scale penal x^(penal-1) Emax sum_l w_l (N phi_l)^T (g_e(U_e) (x) I3) (N phi_l) (w None: all 1); nothing is reduced"""
+        n = len(Phi_list)
+        Va = (C.c_void_p * max(n, 1))(*[_ptr(v) for v in Phi_list])
+        wa = None if w is None else (C.c_double * max(n, 1))(*[float(v) for v in w])
+        _chk(self.L.tp_elasticity_geom_sensitivity(self.handle, n, Va, wa, _ptr(xPhys), _ptr(U), float(Emax), float(penal), float(scale),
+                                                   _ptr(out)), "tp_elasticity_geom_sensitivity")
+
+    def GeomAdjointRHS(self, Phi_list, w, xPhys, Emax, penal, scale, out):
+        """out = scale sum_l w_l d((N phi_l)^T G (N phi_l)) / dU on the owned node planes, supports not applied; ghost planes stay"""
+        n = len(Phi_list)
+        Va = (C.c_void_p * max(n, 1))(*[_ptr(v) for v in Phi_list])
+        wa = None if w is None else (C.c_double * max(n, 1))(*[float(v) for v in w])
+        _chk(self.L.tp_elasticity_geom_adjoint_rhs(self.handle, n, Va, wa, _ptr(xPhys), float(Emax), float(penal), float(scale), _ptr(out)),
+             "tp_elasticity_geom_adjoint_rhs")
+        return out
+
+    def GeomTables(self):
+        """the element's tables (numpy): gradN [8 gp, 3, 8 nodes] and C0 B [8 gp, 6, 24]"""
+        import numpy as np
+        gn, cb = np.zeros(192), np.zeros(1152)
+        _chk(self.L.tp_elasticity_get_geom_tables(self.handle, gn.ctypes.data, cb.ctypes.data), "tp_elasticity_get_geom_tables")
+        return gn.reshape(8, 3, 8), cb.reshape(8, 6, 24)
+
+    def BucklingModes(self, nev, xPhys, Emax, penal, U=None, guard=None, tol=1e-6, max_iter=60):
+        """The nev largest POSITIVE eigenvalues mu of B phi = mu A phi on the CURRENT assembly (xPhys: the design it was made from;
+        U: the state whose stresses make B, default case 0's) -> dict(mu, factor, iters, ksp_its, residuals, gap); the load
+        factors are 1 / mu.  Subspace iteration with Rayleigh-Ritz on a block of q = nev + guard vectors in the manner of
+        Eigenmodes, with these differences: the iteration is Y_j = A^-1 B X_j, warm-started from mu_j X_j; the Ritz problem is
+        eigh(Y^T B Y, Y^T A Y) -- the SPD matrix second (A Y is MatMultKrylov's); B is indefinite, so the block converges to the
+        q eigenvalues of largest MAGNITUDE, of both signs, and the wanted ones are the nev largest positive Ritz values --
+        convergence is tested on those alone, ||B x - mu A x|| / ||B x|| <= tol.  guard None: q = TP_MAX_CASES, which keeps room
+        for the negative ones.  Fewer than nev positive Ritz values in the block at the end, or max_iter reached: TopOptError
+        with the residuals and the Ritz values; no wrong value is returned silently.  The rules for rtol and for several ranks
+        with fewer than two multigrid levels are Eigenmodes'."""
+        import numpy as np
+        import scipy.linalg
+        nev = int(nev)
+        guard = _lib.MAX_CASES - nev if guard is None else int(guard)
+        q = nev + guard
+        if nev < 1 or guard < 0 or q > _lib.MAX_CASES:
+            raise ValueError("BucklingModes: need nev >= 1, guard >= 0 and nev + guard <= TP_MAX_CASES = %d, got %d + %d"
+                             % (_lib.MAX_CASES, nev, guard))
+        if self.grid.part.nranks > 1 and self.opts.nlvls < 2:
+            raise TopOptError(1, "BucklingModes", "BucklingModes failed: TP_ERR_ARG (on %d ranks the solver needs at least two multigrid "
+                              "levels, it has %d)" % (self.grid.part.nranks, self.opts.nlvls))
+        g, sl = self.grid, self.grid.part.owned_slice(3)
+        U = self.U if U is None else U
+        self.GeomAssemble(xPhys, Emax, penal, U)
+        E = self._buck
+        if E is None or E["q"] != q:
+            E = self._buck = dict(q=q, theta=None, X=self._eigen_start(q))
+            for name in ("AX", "BX", "Y", "AY", "BY"):
+                E[name] = [g.node_vec(3) for _ in range(q)]
+        E["nev"], E["mu"], E["U"] = nev, None, U
+        X, AX, BX, Y, AY, BY = (E[k] for k in ("X", "AX", "BX", "Y", "AY", "BY"))
+        own = lambda vs: [v[sl] for v in vs]
+        n_all = X[0].numel()
+        ksp_its, res, npos = 0, None, 0
+
+        def Bmult(v, out):   # B = -N G N
+            self.GeomMult(v, out)
+            _chk(self.L.tp_vec_scale(g.handle, _ptr(out), -1.0, n_all), "tp_vec_scale")
+
+        _chk(self.L.tp_elasticity_set_tolerances(self.handle, min(self.opts.rtol, 0.1 * tol), -1.0, -1.0, -1), "tp_elasticity_set_tolerances")
+        try:
+            for j in range(q):
+                Bmult(X[j], BX[j])
+            for it in range(1, max_iter + 1):
+                for j in range(q):     # Y_j = A^-1 B X_j, from mu_j X_j
+                    if E["theta"] is None:
+                        Y[j].zero_()
+                    else:
+                        Y[j].copy_(X[j])
+                        _chk(self.L.tp_vec_scale(g.handle, _ptr(Y[j]), E["theta"][j], n_all), "tp_vec_scale")
+                    rc, its, _, _, _ = self._solve(BX[j], Y[j])
+                    _chk(rc, "tp_elasticity_solve (buckling modes)")
+                    ksp_its += its
+                    # clamped dofs carry exactly 0 (the preconditioner leaves rounding-sized values there)
+                    _chk(self.L.tp_vec_pointwise(g.handle, _ptr(Y[j]), _ptr(Y[j]), _ptr(self.N), 0, n_all), "tp_vec_pointwise")
+                    self.MatMultKrylov(Y[j], AY[j])
+                    Bmult(Y[j], BY[j])
+                Bt, At = g.BlockGram(own(Y), own(BY)), g.BlockGram(own(Y), own(AY))
+                Bt, At = 0.5 * (Bt + Bt.T), 0.5 * (At + At.T)
+                try:
+                    theta, Q = scipy.linalg.eigh(Bt, At)
+                except (np.linalg.LinAlgError, ValueError) as exc:
+                    raise TopOptError(3, "BucklingModes (Rayleigh-Ritz: the block lost its rank in iteration %d: %s)" % (it, exc))
+                order = np.argsort(-theta)            # the positive ones first, the largest in front
+                theta, Q = theta[order], np.ascontiguousarray(Q[:, order])
+                g.BlockCombine(Y, Q, X)
+                g.BlockCombine(AY, Q, AX)
+                g.BlockCombine(BY, Q, BX)
+                E["theta"] = [float(t) for t in theta]
+                npos = int((theta > 0.0).sum())
+                if npos < nev:
+                    res = None
+                    continue
+                for i in range(nev):   # Y is free until the next solve: B x_i - mu_i A x_i
+                    Y[i].copy_(BX[i])
+                    _chk(self.L.tp_vec_axpby(g.handle, _ptr(Y[i]), -E["theta"][i], _ptr(AX[i]), 1.0, n_all), "tp_vec_axpby")
+                rr, bb = g.BlockGram(own(Y[:nev]), own(Y[:nev])), g.BlockGram(own(BX[:nev]), own(BX[:nev]))
+                res = [float(np.sqrt(rr[i, i] / bb[i, i])) for i in range(nev)]
+                if max(res) <= tol:
+                    break
+            else:
+                ritz = " ".join("%.9e" % t for t in E["theta"])
+                if npos < nev:
+                    err = TopOptError(3, "BucklingModes", "BucklingModes: %d positive Ritz values in the block of %d after %d iterations, "
+                                      "%d wanted (the load does not compress the structure enough, or the block is too small); "
+                                      "Ritz values %s" % (npos, q, max_iter, nev, ritz))
+                else:
+                    err = TopOptError(3, "BucklingModes", "BucklingModes: %d iterations without reaching tol %.1e; residuals %s, Ritz values %s"
+                                      % (max_iter, tol, " ".join("%.3e" % r for r in res), ritz))
+                err.residuals = res
+                raise err
+        finally:
+            rc_restore = self.L.tp_elasticity_set_tolerances(self.handle, self.opts.rtol, -1.0, -1.0, -1)
+        _chk(rc_restore, "tp_elasticity_set_tolerances (restoring rtol)")
+        th = E["theta"]
+        E["mu"] = th[:nev]
+        nxt = max([abs(t) for t in th[nev:]], default=0.0)   # the largest magnitude behind the wanted ones
+        return dict(mu=list(th[:nev]), factor=1.0 / th[0], iters=it, ksp_its=ksp_its, residuals=res,
+                    gap=(1.0 - nxt / th[nev - 1]) if guard > 0 else float("inf"), ritz=list(th))
+
+    def BucklingVectors(self):
+        """the nev fields of the last BucklingModes call, A-normalised (phi_i^T A phi_j = delta_ij); the object's own tensors"""
+        if self._buck is None or self._buck["mu"] is None:
+            raise TopOptError(2, "BucklingVectors (no converged BucklingModes call)")
+        return self._buck["X"][:self._buck["nev"]]
+
+    def BucklingSensitivity(self, out, xPhys, Emin, Emax, penal, P=8.0):
+        """out = dJ/dx of J = (sum_{i < nev} mu_i^P)^(1/P) of the last BucklingModes call -> (J, its), on the CURRENT assembly and
+        the state the modes were made from, for a design-independent load.  With c_i = (mu_i / J)^(P-1):
+        the bilinear pass of Response with U = V = Phi and the weights c_i mu_i (-c_i mu_i phi^T dA/dx phi), the explicit part
+        of the stress stiffness (GeomSensitivity, weights c_i, scale -1), and the state part: the adjoint solve
+        A v = N r, r = -sum c_i d(phi_i^T G phi_i)/du (GeomAdjointRHS), warm-started from the previous call's v, then the bilinear
+        pass with U = u, V = v.  The adjoint solve's figures go to adjoint_its / adjoint_rnorm / adjoint_bnorm."""
+        Phi = self.BucklingVectors()
+        mu, U = self._buck["mu"], self._buck["U"]
+        J = sum(m ** P for m in mu) ** (1.0 / P)
+        c = [(m / J) ** (P - 1.0) for m in mu]
+        if self._buck_adj is None:
+            self._buck_adj, self._buck_rhs = self.grid.node_vec(3), self.grid.node_vec(3)   # (ghost planes of the load stay 0)
+            self._buck_row = self.grid.elem_vec()
+        self.Response(Phi, None, [ci * m for ci, m in zip(c, mu)], xPhys, Emin, Emax, penal, 0.0, dfdx=out, sums=False)
+        self.GeomSensitivity(Phi, c, xPhys, U, Emax, penal, -1.0, out)
+        self.GeomAdjointRHS(Phi, c, xPhys, Emax, penal, -1.0, self._buck_rhs)
+        rc, its, self.adjoint_rnorm, self.adjoint_bnorm, _ = self._solve(self._buck_rhs, self._buck_adj)
+        self.adjoint_its = its
+        _chk(rc, "tp_elasticity_solve (buckling adjoint)")
+        self.Response([U], [self._buck_adj], None, xPhys, Emin, Emax, penal, 0.0, dfdx=self._buck_row, sums=False)
+        _chk(self.L.tp_vec_axpby(self.grid.handle, _ptr(out), 1.0, _ptr(self._buck_row), 1.0, out.numel()), "tp_vec_axpby")
+        return J, its
 
     def KSPSolve(self, hist_cap=0, case=0, rhs=None):
         """solve load case `case` on the last assembly, warm-started from that case's own state (rhs: another right-hand side

@@ -197,3 +197,82 @@ inline void thermal_coupling_box(double dx, double dy, double dz, double nu, dou
     if (g9)
         for (int q = 0; q < 9; q++) g9[q] = m9[q];
 }
+
+// Tables of the geometric (stress) stiffness of the box element, design independent: at the 8 Gauss points of
+// hex8_stiffness_box (same points, loop order a, b, c over xi, eta, zeta, same Jacobian and B accumulation) the physical
+// shape-function gradients gradN[(3 gp + d) * 8 + n] = dN_n/dx_d, and the unit-modulus stress rows
+// cb[(6 gp + r) * 24 + j] = (C0 B(gp))[r][j] (rows xx, yy, zz, xy, yz, zx; engineering shear in B).  The Gauss weight is
+// dx dy dz / 8 for every point.
+inline void hex8_geom_tables_box(double dx, double dy, double dz, double nu, double *gradN /*192*/, double *cb /*1152*/) {
+    const double X[8] = {0.0, dx, dx, 0.0, 0.0, dx, dx, 0.0};
+    const double Y[8] = {0.0, 0.0, dy, dy, 0.0, 0.0, dy, dy};
+    const double Z[8] = {0.0, 0.0, 0.0, 0.0, dz, dz, dz, dz};
+    const double sgx[8] = {-1, 1, 1, -1, -1, 1, 1, -1}, sgy[8] = {-1, -1, 1, 1, -1, -1, 1, 1},
+                 sgz[8] = {-1, -1, -1, -1, 1, 1, 1, 1};
+    const double lambda = nu / ((1.0 + nu) * (1.0 - 2.0 * nu)), mu = 1.0 / (2.0 * (1.0 + nu));
+    double C[6][6] = {};
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++) C[i][j] = lambda;
+        C[i][i] = lambda + 2.0 * mu;
+        C[i + 3][i + 3] = mu;
+    }
+    const int sel[3][6] = {{0, -1, -1, 1, -1, 2}, {-1, 1, -1, 0, 2, -1}, {-1, -1, 2, -1, 1, 0}};
+    const double gp[2] = {-0.577350269189626, 0.577350269189626};
+    int q = 0;
+    for (int a = 0; a < 2; a++)
+        for (int b = 0; b < 2; b++)
+            for (int c = 0; c < 2; c++, q++) {
+                const double xi = gp[a], eta = gp[b], zeta = gp[c];
+                double dN[3][8];
+                for (int n = 0; n < 8; n++) {
+                    dN[0][n] = (sgx[n] * 0.125) * (1.0 + sgy[n] * eta) * (1.0 + sgz[n] * zeta);
+                    dN[1][n] = (sgy[n] * 0.125) * (1.0 + sgx[n] * xi) * (1.0 + sgz[n] * zeta);
+                    dN[2][n] = (sgz[n] * 0.125) * (1.0 + sgx[n] * xi) * (1.0 + sgy[n] * eta);
+                }
+                double J[3][3];
+                for (int r = 0; r < 3; r++) {
+                    double sx = 0.0, sy = 0.0, sz = 0.0;
+                    for (int n = 0; n < 8; n++) {
+                        sx = sx + dN[r][n] * X[n];
+                        sy = sy + dN[r][n] * Y[n];
+                        sz = sz + dN[r][n] * Z[n];
+                    }
+                    J[r][0] = sx;
+                    J[r][1] = sy;
+                    J[r][2] = sz;
+                }
+                const double det = J[0][0] * (J[1][1] * J[2][2] - J[2][1] * J[1][2]) -
+                                   J[0][1] * (J[1][0] * J[2][2] - J[2][0] * J[1][2]) +
+                                   J[0][2] * (J[1][0] * J[2][1] - J[2][0] * J[1][1]);
+                double iJ[3][3];
+                iJ[0][0] = (J[1][1] * J[2][2] - J[2][1] * J[1][2]) / det;
+                iJ[0][1] = -(J[0][1] * J[2][2] - J[0][2] * J[2][1]) / det;
+                iJ[0][2] = (J[0][1] * J[1][2] - J[0][2] * J[1][1]) / det;
+                iJ[1][0] = -(J[1][0] * J[2][2] - J[1][2] * J[2][0]) / det;
+                iJ[1][1] = (J[0][0] * J[2][2] - J[0][2] * J[2][0]) / det;
+                iJ[1][2] = -(J[0][0] * J[1][2] - J[0][2] * J[1][0]) / det;
+                iJ[2][0] = (J[1][0] * J[2][1] - J[1][1] * J[2][0]) / det;
+                iJ[2][1] = -(J[0][0] * J[2][1] - J[0][1] * J[2][0]) / det;
+                iJ[2][2] = (J[0][0] * J[1][1] - J[1][0] * J[0][1]) / det;
+                double B[6][24] = {}, G[3][8] = {};
+                for (int ll = 0; ll < 3; ll++) {
+                    double beta[6][3];
+                    for (int i = 0; i < 6; i++)
+                        for (int j = 0; j < 3; j++)
+                            beta[i][j] = iJ[0][ll] * (sel[0][i] == j ? 1.0 : 0.0) + iJ[1][ll] * (sel[1][i] == j ? 1.0 : 0.0) +
+                                         iJ[2][ll] * (sel[2][i] == j ? 1.0 : 0.0);
+                    for (int i = 0; i < 6; i++)
+                        for (int j = 0; j < 24; j++) B[i][j] = B[i][j] + beta[i][j % 3] * dN[ll][j / 3];
+                    for (int d = 0; d < 3; d++)
+                        for (int n = 0; n < 8; n++) G[d][n] = G[d][n] + iJ[d][ll] * dN[ll][n];
+                }
+                for (int d = 0; d < 3; d++)
+                    for (int n = 0; n < 8; n++) gradN[(3 * q + d) * 8 + n] = G[d][n];
+                for (int r = 0; r < 6; r++)
+                    for (int j = 0; j < 24; j++) {
+                        double s = 0.0;
+                        for (int k = 0; k < 6; k++) s = s + C[r][k] * B[k][j];
+                        cb[(6 * q + r) * 24 + j] = s;
+                    }
+            }
+}

@@ -533,6 +533,12 @@ struct tp_elasticity {
     DevBuf<double> d_mc;         // tp_elasticity_mass_assemble: rho0 V_e m(x_e), own + ghost-above layer (first use)
     double mass_rv = 0.0, mass_xlow = 0.0, mass_invlow = 0.0;   // ... and rho0 V_e, x_low, 1 / x_low of that call
     bool have_mass = false;
+    double GT[1344];             // geometric stiffness tables of the element (elements.h: hex8_geom_tables_box): gradN[192], C0 B[1152]
+    double geom_wq = 0.0;        // ... and the Gauss weight hx hy hz / 8
+    DevBuf<double> d_gtab;       // ... on the device (first tp_elasticity_geom_assemble)
+    DevBuf<double> d_gc;         // tp_elasticity_geom_assemble: Es(x_e) g_e[a,b], 28 planes over own + ghost-above layer (first use)
+    DevBuf<double> d_ges;        // tp_elasticity_geom_adjoint_rhs: Es(x_e), own + ghost-above layer (first use)
+    bool have_geom = false;
     ~tp_elasticity() {
         sym_slot_release(mg.lv[0].sym_slot);
         if (aux_stream) (void)hipStreamDestroy(aux_stream);
@@ -609,6 +615,8 @@ extern "C" int tp_elasticity_create_ke(tp_elasticity **out, tp_grid *g, const tp
     else hex8_stiffness_box(g->o.hx, g->o.hy, g->o.hz, o->nu, e->KE);
     hex8_vonmises_form_box(g->o.hx, g->o.hy, g->o.hz, o->nu, e->VM);
     thermal_coupling_box(g->o.hx, g->o.hy, g->o.hz, o->nu, e->G, e->G9);
+    hex8_geom_tables_box(g->o.hx, g->o.hy, g->o.hz, o->nu, e->GT, e->GT + 192);
+    e->geom_wq = g->o.hx * g->o.hy * g->o.hz / 8.0;
     std::vector<double> M(8 * 576);
     host_child_matrices(e->KE, M.data());
     TP_TRY(e->mg.alloc_levels());
@@ -1390,13 +1398,14 @@ extern "C" int tp_elasticity_last_op_form(const tp_elasticity *e, int *form4) {
 
 // ===========================================================================
 // responses of the state: compliance of one or several load cases, von Mises stress p-norm, self-weight, thermal expansion, the mass operator and
-// the block-vector passes of the eigen-solver
+// the block-vector passes of the eigen-solver, the geometric stiffness of the buckling analysis
 // ===========================================================================
 #include "response.h"
 #include "stress.h"
 #include "bodyforce.h"
 #include "thermoelastic.h"
 #include "mass.h"
+#include "geomstiff.h"
 #include "blockvec.h"
 
 // ===========================================================================

@@ -119,6 +119,23 @@ class TopOpt:
     frequency_rho: float = 1.0
     frequency_xlow: float = 0.1
     frequency_tol: float = 1e-6
+    # buckling constraint: the linear buckling load factors of load case buckling_case, 1 / mu_i for the positive
+    # eigenvalues of -G(x, u) phi = mu K phi, held above buckling_limit through the p-norm of the buckling_modes largest mu:
+    # g = buckling_limit (sum mu_i^buckling_P)^(1/buckling_P) - 1 as an MMA constraint behind the frequency row, on xPrint and the
+    # assembly and state of the state solve; the modes are found by subspace iteration to the residual buckling_tol and
+    # warm-started from the previous design iteration, the gradient carries an adjoint solve.  For design-independent loads
+    # only: not together with body_force or thermoelastic physics (None: none, nothing changes)
+    buckling_limit: float = None
+    buckling_modes: int = 2
+    buckling_P: float = 8.0
+    buckling_tol: float = 1e-6
+    buckling_case: int = 0
+    # the primary load: "cantilever", the reference's line load, or "axial", a uniform traction along -x on the face x = xmax,
+    # total 1, behind the same clamped face x = xmin -- a column in compression, the load a buckling user starts from; the name is
+    # accepted in loadcases too.  (Under the reference's line load the spectrum of the buckling pencil has both signs with
+    # clustered magnitudes -- on 12x8x4 the largest positive mu sits behind five larger negative ones at a ratio of 0.87 -- so the
+    # block iteration converges slowly there: a poor first target for the buckling constraint.)
+    load: str = "cantilever"
     # passive regions: the global label array (natural order; 0 active, 1 void, 2 solid) or a list of shapes for
     # api.passive_labels.  Void elements are held at x = Xmin, xPhys = 0, solid ones at x = Xmax, xPhys = 1; MMA works on the
     # active elements alone, packed; the volume constraint stays the mean over ALL elements (None: none, nothing changes)
@@ -213,6 +230,29 @@ class TopOpt:
             self.frequency_modes = int(self.frequency_modes)
             self._k_freq = 1 + (self.stress_limit is not None) + (self.local_volume is not None)
             self.m = max(self.m, self._k_freq + 1)
+        if self.load not in ("cantilever", "axial"):
+            raise ValueError("load must be 'cantilever' or 'axial', got %r" % (self.load,))
+        if self.load == "axial" and self.physics_kind == "heat":
+            raise ValueError("load='axial' belongs to the elastic problems, got physics='heat'")
+        self._k_buck = None
+        if self.buckling_limit is not None:
+            import math
+            if not (self.buckling_limit > 0.0 and math.isfinite(self.buckling_limit)):
+                raise ValueError("buckling_limit must be positive and finite")
+            if isinstance(self.buckling_modes, bool) or int(self.buckling_modes) != self.buckling_modes or not 1 <= self.buckling_modes <= 4:
+                raise ValueError("buckling_modes: 1 to 4 (the block of 8 vectors keeps as many again for the negative eigenvalues)")
+            if not (self.buckling_P >= 1.0 and math.isfinite(self.buckling_P)):
+                raise ValueError("buckling_P must be at least 1 and finite")
+            if not (self.buckling_tol > 0.0 and math.isfinite(self.buckling_tol)):
+                raise ValueError("buckling_tol must be positive and finite")
+            ncases = 1 + len(self.loadcases or ())
+            if isinstance(self.buckling_case, bool) or int(self.buckling_case) != self.buckling_case or not 0 <= self.buckling_case < ncases:
+                raise ValueError("buckling_case must name one of the %d load cases" % ncases)
+            if self.body_force is not None:
+                raise ValueError("buckling_limit together with body_force is not supported: the gradient holds for a design-independent load")
+            self.buckling_modes, self.buckling_case = int(self.buckling_modes), int(self.buckling_case)
+            self._k_buck = 1 + (self.stress_limit is not None) + (self.local_volume is not None) + (self.frequency_limit is not None)
+            self.m = max(self.m, self._k_buck + 1)
         nx, ny, nz = self.nxyz
         h = ((self.xc[1] - self.xc[0]) / (nx - 1), (self.xc[3] - self.xc[2]) / (ny - 1),
              (self.xc[5] - self.xc[4]) / (nz - 1))
@@ -227,7 +267,10 @@ class TopOpt:
         self.grid = Grid(nx, ny, nz, h, rank=self.rank, nranks=self.nranks)
         so = self.solver or SolverOptions(nlvls=self.nlvls, nu=self.nu)
         self.physics = (HeatConduction if self.physics_kind == "heat" else LinearElasticity)(self.grid, so)
-        self.physics.SetUpLoadAndBC()
+        if self.load == "axial":
+            self.physics.SetUpLoadAndBC_Axial()
+        else:
+            self.physics.SetUpLoadAndBC()
         if self.physics_kind == "thermoelastic":
             self._setup_thermoelastic(so)
         else:
@@ -242,9 +285,12 @@ class TopOpt:
                 self.physics.RHS.zero_()
         for rhs, weight in (self.loadcases or ()):
             if isinstance(rhs, str):
-                if rhs != "top":
-                    raise ValueError("unknown load case %r (the only name is 'top')" % (rhs,))
-                self.physics.SetUpLoadAndBC_Top(weight)
+                if rhs == "axial":
+                    self.physics.AddLoadCase(self.physics.AxialLoad(), weight)
+                elif rhs == "top":
+                    self.physics.SetUpLoadAndBC_Top(weight)
+                else:
+                    raise ValueError("unknown load case %r (the names are 'top' and 'axial')" % (rhs,))
             else:
                 self.physics.AddLoadCase(rhs, weight)
         self.filt = Filter(self.grid, self.filter, self.rmin)
@@ -308,7 +354,8 @@ class TopOpt:
         """heat conduction's refusals; host arithmetic on the parameters, before any device object"""
         import math
         for name, what in (("loadcases", "further load cases"), ("stress_limit", "the stress constraint"), ("body_force", "self-weight"),
-                           ("frequency_limit", "the eigenfrequency constraint"), ("robust", "robust design"), ("overhang", "the overhang filter"),
+                           ("frequency_limit", "the eigenfrequency constraint"), ("buckling_limit", "the buckling constraint"), ("robust", "robust design"),
+                           ("overhang", "the overhang filter"),
                            ("local_volume", "the local volume constraint"), ("length_scale", "the length-scale constraints")):
             if getattr(self, name) is not None:
                 raise ValueError("physics='heat' together with %s (%s) is not supported" % (name, what))
@@ -323,7 +370,8 @@ class TopOpt:
         """the thermoelastic problem's refusals; host arithmetic on the parameters, before any device object"""
         import math
         for name, what in (("loadcases", "further load cases"), ("stress_limit", "the stress constraint"), ("body_force", "self-weight"),
-                           ("frequency_limit", "the eigenfrequency constraint"), ("robust", "robust design"), ("overhang", "the overhang filter"),
+                           ("frequency_limit", "the eigenfrequency constraint"), ("buckling_limit", "the buckling constraint"), ("robust", "robust design"),
+                           ("overhang", "the overhang filter"),
                            ("local_volume", "the local volume constraint"), ("length_scale", "the length-scale constraints")):
             if getattr(self, name) is not None:
                 raise ValueError("physics='thermoelastic' together with %s (%s) is not supported" % (name, what))
@@ -413,7 +461,7 @@ class TopOpt:
         if self.body_force is not None:
             raise ValueError("robust together with body_force is not supported: with a load that grows with the density the "
                              "eroded design is no longer the worst of the three")
-        for name in ("stress_limit", "local_volume", "frequency_limit", "overhang", "length_scale"):
+        for name in ("stress_limit", "local_volume", "frequency_limit", "buckling_limit", "overhang", "length_scale"):
             if getattr(self, name) is not None:
                 raise ValueError("robust together with %s is not supported: the constraint would have to choose a realisation" % name)
         self.robust, self.eta = etas, etas[1]
@@ -549,6 +597,15 @@ class TopOpt:
             row.mul_(self.frequency_limit / self.frequency_modes)
             g_freq = self.frequency_limit / self.frequency_modes * J - 1.0
             gxs.append(g_freq)
+        if self.buckling_limit is not None:    # on the assembly and the state of the solve above; modes and adjoint warm-start
+            ph = self.physics
+            buck = ph.BucklingModes(self.buckling_modes, self.xPrint, self.Emax, self.penal, U=ph.LoadCaseU(self.buckling_case),
+                                    tol=self.buckling_tol)
+            row = self.dgdx[self._k_buck]
+            J_buck, its_buck = ph.BucklingSensitivity(row, self.xPrint, self.Emin, self.Emax, self.penal, self.buckling_P)
+            row.mul_(self.buckling_limit)
+            g_buck = self.buckling_limit * J_buck - 1.0
+            gxs.append(g_buck)
         rows = self.dgdx   # what goes back through the overhang filter and the projection: every row but the length scale's
         if self.lengthscale is not None:    # on the blueprint (xTilde, xPhys); d/dxTilde, the projection's derivative inside
             rows, lrows = self.dgdx[:self._k_length[0]], [self.dgdx[k] for k in self._k_length]
@@ -606,6 +663,9 @@ class TopOpt:
         if self.frequency_limit is not None:
             rec["eig"], rec["gx_frequency"], rec["eig_iters"] = list(eig["lam"]), g_freq, eig["iters"]
             rec["ksp_its_eigen"], rec["eig_gap"] = eig["ksp_its"], eig["gap"]
+        if self.buckling_limit is not None:
+            rec["buckling_mu"], rec["buckling_factor"], rec["gx_buckling"] = list(buck["mu"]), buck["factor"], g_buck
+            rec["buckling_iters"], rec["ksp_its_buckling"], rec["buckling_gap"] = buck["iters"], buck["ksp_its"] + its_buck, buck["gap"]
         if self.lengthscale is not None:
             rec["gx_solid"], rec["gx_void"] = ls["g_solid"], ls["g_void"]
             rec["length_S_solid"], rec["length_S_void"] = ls["S_solid"], ls["S_void"]

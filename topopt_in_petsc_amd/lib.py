@@ -124,6 +124,11 @@ SYMBOLS = {
     "tp_elasticity_mass_assemble": (_i, [_vp, _vp, _d, _d]),
     "tp_elasticity_mass_apply": (_i, [_vp, _vp, _vp]),
     "tp_elasticity_mass_sensitivity": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_d), _vp, _d, _vp]),
+    "tp_elasticity_geom_assemble": (_i, [_vp, _vp, _vp, _d, _d]),
+    "tp_elasticity_geom_apply": (_i, [_vp, _vp, _vp]),
+    "tp_elasticity_geom_sensitivity": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_d), _vp, _vp, _d, _d, _d, _vp]),
+    "tp_elasticity_geom_adjoint_rhs": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_d), _vp, _d, _d, _d, _vp]),
+    "tp_elasticity_get_geom_tables": (_i, [_vp, _vp, _vp]),
     "tp_elasticity_petsc_options": (_i, [_vp, C.c_char_p, C.c_size_t]),
     "tp_elasticity_level_count": (_i, [_vp]),
     "tp_elasticity_level_nodes": (_l, [_vp, _i]),
