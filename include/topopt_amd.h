@@ -630,6 +630,31 @@ int tp_overhang_forward(tp_overhang *ov, const double *x, double *xi);   /* TP_E
 int tp_overhang_adjoint(tp_overhang *ov, int nvec, double *const *g);
 int tp_overhang_last_chunk(const tp_overhang *ov);              /* layers per launch of the last sweep */
 
+/* ---- casting (draw-direction) filter (no reference counterpart) ---- */
+/* A "cast" density c built from the blueprint density x line by line along the draw axis: a part that leaves a mould along that
+ * axis has no undercut and no enclosed cavity, so along every line of elements c falls monotonically away from the mould's
+ * base.  Axis 0 (x), 1 (y) or 2 (z) with n global element layers; the parting index p in [0, n] splits every line: the cells
+ * k >= p (upper die, withdrawn towards +axis) become non-increasing in k, the cells k < p (lower die) non-decreasing.  p = 0 is
+ * the one-sided draw "+axis" (the part sits on a base at the lowest index), p = n is "-axis", between them a two-sided mould
+ * with a plane parting surface between the layers p - 1 and p.  Upper range, from k = n - 1 down to p (the lower range is the
+ * mirror image from k = 0 up to p - 1):
+ *   c_{n-1} = x_{n-1};  d = x_k - c_{k+1},  rho = sqrt(d^2 + eps),  c_k = (x_k + c_{k+1} + rho) / 2
+ *   (a smooth running maximum, no clamp: with m steps behind it  hardmax <= c <= hardmax + m sqrt(eps) / 2;  default eps = 1e-6)
+ * A filter, not a constraint: the responses are evaluated on c and their gradients come back through the transpose of the
+ * sweep's Jacobian, which works in place on up to 8 vectors at once from one coefficient array the forward sweep left in the
+ * handle.  All arrays [dev, own elements].  No line has a neighbour, so x and y draws are rank-local on z-slabs; a z draw runs
+ * as a pipeline over the slabs, one after the other, and gives the results of one rank bit for bit.  The x draw has two kernel
+ * forms with equal bits, chosen per call by TP_CASTING_XFORM. */
+typedef struct tp_casting tp_casting;
+int tp_casting_create(tp_casting **c, tp_grid *g, int axis /*0 x, 1 y, 2 z*/, int parting /*0 .. n_axis global*/);
+int tp_casting_destroy(tp_casting *c);                          /* NULL: 0 */
+/* TP_ERR_ARG unless eps > 0 and finite; a forward call must follow before the next transpose */
+int tp_casting_set_params(tp_casting *c, double eps);
+int tp_casting_forward(tp_casting *c, const double *x, double *out);   /* TP_ERR_ARG if x == out */
+/* g[v] <- J^T g[v], v < nvec, 1 <= nvec <= 8; TP_ERR_ARG without a forward call on this handle before it */
+int tp_casting_adjoint(tp_casting *c, int nvec, double *const *g);
+int tp_casting_last_form(const tp_casting *c);                  /* 1 walk, 2 LDS-staged x, 3 strided x walk */
+
 /* ---- passive regions: elements held at a fixed density (no reference counterpart) ---- */
 /* Labels per own element, natural order: 0 active, 1 void, 2 solid.  The optimiser works on the active elements alone, packed in
  * ascending element order (n_active entries); the filter and the physics work on the full fields (all own elements) with the

@@ -1,12 +1,14 @@
 #!/usr/bin/env python
 """End-to-end run of the reference's optimisation loop on the MI355X path.
-usage: run_topopt.py [--physics elasticity|heat|thermoelastic [--alpha A] [--thermal uniform:DT] [--t-ref T] [--thermal-penal P]] [--loadcase top[:weight]]... [--stress-limit L [--stress-p P] [--stress-q q]] [--local-volume ALPHA:R] [--overhang +z|-z|+y|-y] [--self-weight bx,by,bz[:xlow] [--no-point-load]] [--length-scale both|solid|void[:C]] [--frequency-limit L[:nev]] [--load cantilever|axial] [--buckling-limit L[:nev]] [--passive solid|void:box|sphere|cylinder:numbers]... [--robust ETA_E,ETA_N,ETA_D[:every]] ex ey ez nlvls n_iter [filter [nsmooth ncoarse]]
+usage: run_topopt.py [--physics elasticity|heat|thermoelastic [--alpha A] [--thermal uniform:DT] [--t-ref T] [--thermal-penal P]] [--loadcase top[:weight]]... [--stress-limit L [--stress-p P] [--stress-q q]] [--local-volume ALPHA:R] [--overhang +z|-z|+y|-y] [--casting DRAW [--casting-eps E]] [--self-weight bx,by,bz[:xlow] [--no-point-load]] [--length-scale both|solid|void[:C]] [--frequency-limit L[:nev]] [--load cantilever|axial] [--buckling-limit L[:nev]] [--passive solid|void:box|sphere|cylinder:numbers]... [--robust ETA_E,ETA_N,ETA_D[:every]] ex ey ez nlvls n_iter [filter [nsmooth ncoarse]]
 (e.g. 128 128 128 5 20 1 2 45: the cycle of bench.py; --loadcase top:0.5 adds the line load on the upper edge as a second load
 case of weight 0.5 -- the objective becomes the weighted sum of the cases' compliances; --stress-limit L holds the von Mises
 p-norm of load case 0 below L as a second constraint, exponent --stress-p (8), stress relaxation x^q with --stress-q (0.5); --local-volume ALPHA:R holds the mean density in a ball of
 radius R (a length, the element size is 1/ey) around every element below ALPHA through one p-norm constraint, exponent 16, as
 the last constraint; --overhang DIR evaluates every response on the printed density of a part built layer by layer along DIR, the
-overhang filter of DESIGN 4.11; --self-weight bx,by,bz[:xlow] adds the structure's own weight, a body force (per unit volume at full
+overhang filter of DESIGN 4.11; --casting DRAW evaluates every response on the density of a part that leaves its mould along DRAW
+without undercut or cavity, the casting filter of DESIGN 4.20: +x .. -z for a one-sided mould, x:K, y:K or z:K for a two-sided one
+parted between the element layers K - 1 and K, smoothing --casting-eps (1e-6), not together with --overhang; --self-weight bx,by,bz[:xlow] adds the structure's own weight, a body force (per unit volume at full
 density) that moves with the design, the mass of elements below xlow (0.1) damped, DESIGN 4.12 -- with --no-point-load it is the only
 load; --length-scale KINDS[:C] holds a minimum length scale of the solid and / or the void phase by the geometric constraints of
 DESIGN 4.13 as the last constraints, decay C in length^2 (default rmin^4 / h^2), with the Heaviside projection switched on;
@@ -73,6 +75,8 @@ if local_volume is not None:
         sys.exit("--local-volume needs ALPHA:R, got %r" % local_volume)
     local = dict(local_volume=float(alpha), local_volume_R=float(radius))
 overhang, self_weight = _last("--overhang"), _last("--self-weight")
+casting_draw, casting_eps = _last("--casting"), _last("--casting-eps", float)
+casting = {} if casting_draw is None else dict(casting=casting_draw, **({} if casting_eps is None else dict(casting_eps=casting_eps)))
 no_point_load = "--no-point-load" in sys.argv[1:]
 sys.argv[1:] = [a for a in sys.argv[1:] if a != "--no-point-load"]
 body = {}
@@ -151,7 +155,7 @@ ex, ey, ez, nlv, nit = [int(v) for v in sys.argv[1:6]]
 flt = int(sys.argv[6]) if len(sys.argv) > 6 else 1
 h = 1.0 / ey
 opt = tp.TopOpt(nxyz=(ex + 1, ey + 1, ez + 1), xc=(0, ex * h, 0, 1, 0, ez * h), nlvls=nlv, rmin=2.56 * h, filter=flt,
-                loadcases=loadcases or None, **stress, **local, overhang=overhang, **body, **length, **frequency, load=load_arg, **buckling, passive=shapes or None, **robust, physics=physics, **thermo,
+                loadcases=loadcases or None, **stress, **local, overhang=overhang, **casting, **body, **length, **frequency, load=load_arg, **buckling, passive=shapes or None, **robust, physics=physics, **thermo,
                 solver=tp.SolverOptions(nlvls=nlv, **(dict(nsmooth=int(sys.argv[7]), ncoarse=int(sys.argv[8])) if len(sys.argv) > 8 else {})))
 print("# %dx%dx%d elements, %d DOF, %d MG levels, filter %d, rmin %.4f" % (ex, ey, ez, (1 if physics == "heat" else 3) * (ex + 1) * (ey + 1) * (ez + 1), nlv, flt, 2.56 * h))
 for it in range(nit):
@@ -164,6 +168,8 @@ for it in range(nit):
               % (r["stress_pnorm"], r["stress_max"], r["gx_stress"], r["ksp_its_adjoint"]), flush=True)
     if "print_loss" in r:
         print("Overhang:      build %s, mean(xPhys - xPrint): %f" % (overhang, r["print_loss"]), flush=True)
+    if "cast_fill" in r:
+        print("Casting:       draw %s, mean(xPrint - xPhys): %f" % (casting_draw, r["cast_fill"]), flush=True)
     if "ksp_its_thermal" in r:
         print("Thermoelastic: T max: %e | conduction iter: %d, thermal adjoint iter: %d" % (r["T_max"], r["ksp_its_thermal"], r["ksp_its_thermal_adjoint"]), flush=True)
     if "body_share" in r:

@@ -1828,6 +1828,65 @@ class Overhang:
         return self.L.tp_overhang_last_chunk(self.handle)
 
 
+class Casting:
+    """Casting (draw-direction) filter (tp_casting): the density of a part that leaves its mould along `draw` without an
+    undercut or an enclosed cavity, and the transpose of its Jacobian.  `draw`: "+x", "-x", "+y", "-y", "+z", "-z" -- a
+    one-sided mould, the part sitting on a base at the low end for + -- or "x:K", "y:K", "z:K", a two-sided mould whose plane
+    parting surface lies between the element layers K - 1 and K (global)."""
+    AXES = {"x": 0, "y": 1, "z": 2}
+
+    @classmethod
+    def parse(cls, draw, ne=None):
+        """-> (axis, parting) of a draw string; parting is None for "-a" while the element counts `ne` are not given.
+        ValueError for anything else, and with `ne` for a K outside 1 .. n - 1"""
+        ok = isinstance(draw, str) and len(draw) >= 2
+        if ok and draw[0] in "+-" and len(draw) == 2 and draw[1] in cls.AXES:
+            axis = cls.AXES[draw[1]]
+            return axis, (0 if draw[0] == "+" else (None if ne is None else ne[axis]))
+        if ok and draw[0] in cls.AXES and draw[1] == ":" and draw[2:].isdigit():
+            axis, k = cls.AXES[draw[0]], int(draw[2:])
+            if k >= 1 and (ne is None or k <= ne[axis] - 1):
+                return axis, k
+        raise ValueError('draw must be "+a" or "-a" with a in x, y, z, or "a:K" with 1 <= K <= n_a - 1, got %r' % (draw,))
+
+    def __init__(self, grid, draw="+z"):
+        p = grid.part
+        self.axis, self.parting = self.parse(draw, (p.ex, p.ey, p.ez))
+        self.grid, self.L, self.draw = grid, grid.L, draw
+        self.handle = C.c_void_p()
+        _chk(self.L.tp_casting_create(C.byref(self.handle), grid.handle, self.axis, self.parting), "tp_casting_create")
+        grid._adopt(self)
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.L.tp_casting_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def params(self, eps=1e-6):
+        _chk(self.L.tp_casting_set_params(self.handle, eps), "tp_casting_set_params")
+
+    def Forward(self, x, out):
+        """out = cast density of x (out must not be x); leaves the coefficients of the transpose in the handle"""
+        _chk(self.L.tp_casting_forward(self.handle, _ptr(x), _ptr(out)), "tp_casting_forward")
+        return out
+
+    def Adjoint(self, vecs):
+        """every tensor of the list (1 to 8) becomes J^T times itself, in place, in one sweep"""
+        ptrs = (C.c_void_p * len(vecs))(*[_ptr(v) for v in vecs])
+        _chk(self.L.tp_casting_adjoint(self.handle, len(vecs), ptrs), "tp_casting_adjoint")
+        return vecs
+
+    def last_form(self):
+        """kernel form of the last sweep: 1 walk, 2 LDS-staged x draw, 3 walk on x lines (TP_CASTING_XFORM=0)"""
+        return self.L.tp_casting_last_form(self.handle)
+
+
 class MMA:
     """MMA (MMA.h:29-140) on the device: the design vectors stay in HBM."""
 

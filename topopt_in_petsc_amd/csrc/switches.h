@@ -302,6 +302,12 @@ inline int sw_overhang_chunk() {
     const int c = sw_int("TP_OVERHANG_CHUNK", 4);
     return (c == 1 || c == 2 || c == 4 || c == 8) ? c : 4;
 }
+// TP_CASTING_XFORM=0|1 (default 1; any other value counts as unset): form of the casting filter's x draw (casting.h), 1 the
+// LDS-staged kernels, 0 the walk kernels on x lines; both give the same bits, tp_casting_last_form reports what ran (2 or 3)
+inline bool sw_casting_xform() {
+    const int v = sw_int("TP_CASTING_XFORM", 1);
+    return v != 0;
+}
 // TP_NO_GRAPH set (default graphs): the Lanczos chains are enqueued, not captured and replayed.  Read per call by
 // lanczos_graph_replayable; lanczos_graph latches it on its first run (mg_spectra.h), as before.
 inline bool sw_no_graph() { return sw_set("TP_NO_GRAPH"); }

@@ -1434,6 +1434,11 @@ extern "C" int tp_elasticity_last_op_form(const tp_elasticity *e, int *form4) {
 #include "overhang.h"
 
 // ===========================================================================
+// casting (draw-direction) filter: line sweeps along the draw axis
+// ===========================================================================
+#include "casting.h"
+
+// ===========================================================================
 // passive regions: fixed solid / void elements beside the packed design
 // ===========================================================================
 #include "passive.h"

@@ -16,7 +16,7 @@ import torch
 from . import mpiio
 import ctypes as C
 
-from .api import Filter, Grid, HeatConduction, LengthScale, LinearElasticity, LocalVolume, MMA, Overhang, Passive, Robust, SolverOptions, _chk, _ptr, check_body_force, check_thermal, passive_labels
+from .api import Casting, Filter, Grid, HeatConduction, LengthScale, LinearElasticity, LocalVolume, MMA, Overhang, Passive, Robust, SolverOptions, _chk, _ptr, check_body_force, check_thermal, passive_labels
 
 
 def robust_volume_target(volfrac, S_d, S_n):
@@ -92,6 +92,13 @@ class TopOpt:
     # response is evaluated on xPrint = Overhang.Forward(xPhys) and its gradient comes back through Overhang.Adjoint (None:
     # xPrint is xPhys itself, nothing changes)
     overhang: str = None
+    # casting (draw-direction) filter: "+x" .. "-z", a one-sided mould withdrawn along that axis, or "x:K", "y:K",
+    # "z:K", a two-sided one parted between the element layers K - 1 and K.  Every response is evaluated on xPrint = Casting.
+    # Forward(xPhys), which has no undercut and no cavity along the axis, and its gradient comes back through Casting.Adjoint.
+    # casting_eps: the smoothing of the running maximum; a run of m void cells rises to sqrt(m eps / 2) at most, 0.008 over 128
+    # cells at the default.  Not together with overhang: both define xPrint (None: xPrint is xPhys itself, nothing changes)
+    casting: str = None
+    casting_eps: float = 1e-6
     # self-weight: body_force = (b_x, b_y, b_z), the body force per unit volume at full density (rho g), as a load that moves
     # with xPrint beside the fixed ones; the mass of elements below body_force_xlow is damped.  point_load=False
     # zeroes case 0's fixed load: a part that carries its own weight only (None: no body force, nothing changes)
@@ -183,6 +190,13 @@ class TopOpt:
             self._check_robust()
         if self.overhang is not None and self.overhang not in Overhang.BUILDS:
             raise ValueError("overhang must be None or one of %s, got %r" % (", ".join(sorted(Overhang.BUILDS)), self.overhang))
+        if self.casting is not None:
+            import math
+            if self.overhang is not None:
+                raise ValueError("casting together with overhang is not supported: both define xPrint")
+            Casting.parse(self.casting, tuple(n - 1 for n in self.nxyz))
+            if not (isinstance(self.casting_eps, (int, float)) and math.isfinite(self.casting_eps) and self.casting_eps > 0.0):
+                raise ValueError("casting_eps must be positive and finite, got %r" % (self.casting_eps,))
         if self.body_force is not None:
             self.body_force, self.body_force_xlow = check_body_force(self.body_force, self.body_force_xlow)
         else:
@@ -297,11 +311,15 @@ class TopOpt:
         self.localvol = LocalVolume(self.grid, self.local_volume_R) if self.local_volume is not None else None
         self.overhang_filter = Overhang(self.grid, self.overhang) if self.overhang is not None else None
         self.lengthscale = LengthScale(self.grid) if self.length_scale is not None else None
+        self.casting_filter = None
+        if self.casting is not None:
+            self.casting_filter = Casting(self.grid, self.casting)
+            self.casting_filter.params(self.casting_eps)
         g = self.grid
         # TopOpt.cc:362-381: all design fields start at volfrac
         self.x = g.elem_vec(self.volfrac)
         self.xTilde, self.xPhys = g.elem_vec(self.volfrac), g.elem_vec(self.volfrac)
-        self.xPrint = g.elem_vec(self.volfrac) if self.overhang_filter is not None else self.xPhys
+        self.xPrint = g.elem_vec(self.volfrac) if (self.overhang_filter or self.casting_filter) is not None else self.xPhys
         self.projector, self.vd_target, self._S = None, None, None
         if self.robust is not None:
             self.projector = Robust(g)
@@ -355,7 +373,7 @@ class TopOpt:
         import math
         for name, what in (("loadcases", "further load cases"), ("stress_limit", "the stress constraint"), ("body_force", "self-weight"),
                            ("frequency_limit", "the eigenfrequency constraint"), ("buckling_limit", "the buckling constraint"), ("robust", "robust design"),
-                           ("overhang", "the overhang filter"),
+                           ("overhang", "the overhang filter"), ("casting", "the casting filter"),
                            ("local_volume", "the local volume constraint"), ("length_scale", "the length-scale constraints")):
             if getattr(self, name) is not None:
                 raise ValueError("physics='heat' together with %s (%s) is not supported" % (name, what))
@@ -371,7 +389,7 @@ class TopOpt:
         import math
         for name, what in (("loadcases", "further load cases"), ("stress_limit", "the stress constraint"), ("body_force", "self-weight"),
                            ("frequency_limit", "the eigenfrequency constraint"), ("buckling_limit", "the buckling constraint"), ("robust", "robust design"),
-                           ("overhang", "the overhang filter"),
+                           ("overhang", "the overhang filter"), ("casting", "the casting filter"),
                            ("local_volume", "the local volume constraint"), ("length_scale", "the length-scale constraints")):
             if getattr(self, name) is not None:
                 raise ValueError("physics='thermoelastic' together with %s (%s) is not supported" % (name, what))
@@ -461,7 +479,7 @@ class TopOpt:
         if self.body_force is not None:
             raise ValueError("robust together with body_force is not supported: with a load that grows with the density the "
                              "eroded design is no longer the worst of the three")
-        for name in ("stress_limit", "local_volume", "frequency_limit", "buckling_limit", "overhang", "length_scale"):
+        for name in ("stress_limit", "local_volume", "frequency_limit", "buckling_limit", "overhang", "casting", "length_scale"):
             if getattr(self, name) is not None:
                 raise ValueError("robust together with %s is not supported: the constraint would have to choose a realisation" % name)
         self.robust, self.eta = etas, etas[1]
@@ -552,6 +570,8 @@ class TopOpt:
         """xPrint follows every FilterProject"""
         if self.overhang_filter is not None:
             self.overhang_filter.Forward(self.xPhys, self.xPrint)
+        if self.casting_filter is not None:
+            self.casting_filter.Forward(self.xPhys, self.xPrint)
 
     def step(self, verbose=False):
         """one pass of the loop body, main.cc:54-111; returns the record of this iteration"""
@@ -623,6 +643,8 @@ class TopOpt:
                 gxs.extend(g_length)
         if self.overhang_filter is not None:   # d/dxPrint -> d/dxPhys, all of them in one sweep
             self.overhang_filter.Adjoint([self.dfdx] + rows)
+        if self.casting_filter is not None:
+            self.casting_filter.Adjoint([self.dfdx] + rows)
         if self.robust is not None:    # d/dxErode and d/dxDilate -> d/dxTilde, passive entries zeroed, in one launch; then the filter
             self.projector.Chain(self.xTilde, self.beta, [self.dfdx, self.dgdx[0]], [self.robust[0], self.robust[2]], passive=self.regions)
             self.filt.GradientsFromTilde(self.x, [self.dfdx, self.dgdx[0]])
@@ -671,6 +693,8 @@ class TopOpt:
             rec["length_S_solid"], rec["length_S_void"] = ls["S_solid"], ls["S_void"]
         if self.overhang_filter is not None:
             rec["print_loss"] = self._mean(self.xPhys - self.xPrint)
+        if self.casting_filter is not None:
+            rec["cast_fill"] = self._mean(self.xPrint - self.xPhys)
         if self.body_force is not None:
             rec["body_share"] = body_share
         if self.physics_kind == "thermoelastic":
