@@ -56,6 +56,9 @@ def _dmass64(x, x_low):
     return np.where(x >= x_low, 1.0, (t * t) * (t * t) * t * (36.0 - 35.0 * t))
 
 
+mass64, dmass64 = _mass64, _dmass64        # (the names for other helper modules: tests/response_rowwise.py)
+
+
 def mass_apply(x, dofs, nnode, h, rho0, x_low, N, u, dtype=LD):
     """y = N M N u, element by element"""
     Nv = np.asarray(N, dtype=dtype)

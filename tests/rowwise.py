@@ -147,6 +147,9 @@ def _pow2(v):
     return 1 << int(np.ceil(np.log2(v)))
 
 
+pow2 = _pow2        # (the name for other helper modules: tests/response_rowwise.py)
+
+
 # =====================================================================================================================
 # the Helmholtz (PDE) filter's scalar hierarchy (tests/test_gpu_pde_rowwise.py): K_f of an anisotropic box, one 8 x 8 matrix per
 # level, no moduli and no Dirichlet rows.  Row scales: level l  |K_f|_l |u| -- the hierarchy assembled from abs(kf) applied to
@@ -554,6 +557,9 @@ def _describe(row, where):
     what = "node" if dof else "element"
     return ("%s (%d, %d, %d)%s, i mod 15 = %d, i mod 31 = %d, j mod 7 = %d, plane offset in its z-chunk (kz %s) = %s"
             % (what, i, j, k, " component %d" % c if dof else "", i % 15, i % 31, j % 7, kz or "-", (k - where.get("k0", 0)) % kz if kz else "-"))
+
+
+describe = _describe        # (the name for other helper modules: tests/response_rowwise.py)
 
 
 def assert_rowwise(got, ref_ld, scale, c, where):
