@@ -91,6 +91,7 @@ def lib():
         L.orc_mnd.argtypes = [C.c_long, C.c_void_p]
         L.orc_heaviside.argtypes = [C.c_long, C.c_void_p, c_real, c_real, C.c_void_p]
         L.orc_heaviside_chain.argtypes = [C.c_long, C.c_void_p, c_real, c_real, C.c_void_p]
+        L.orc_pointwise_divide.argtypes = [C.c_long, C.c_void_p, C.c_void_p, C.c_void_p]
         L.orc_pdef_create.restype = C.c_void_p
         L.orc_pdef_create.argtypes = [C.c_int] * 3 + [c_real] * 4 + [C.c_int] * 3 + [c_real] * 2
         L.orc_pdef_destroy.argtypes = [C.c_void_p]
@@ -416,6 +417,14 @@ def heaviside_chain(xt, beta, eta):
 def mnd(x):
     x = f64(x)
     return lib().orc_mnd(x.size, _p(x))
+
+
+def pointwise_divide(x, y):
+    """w = x / y as PETSc's VecPointwiseDivide defines it: 0 where y is 0"""
+    x, y = f64(x), f64(y)
+    w = np.zeros_like(x)
+    lib().orc_pointwise_divide(x.size, _p(x), _p(y), _p(w))
+    return w
 
 
 class MMA:

@@ -1321,6 +1321,13 @@ ORC_API double orc_mnd(long n, const double *x) {
     return s / (double)n;
 }
 
+/* VecPointwiseDivide as PETSc documents it: the quotient, 0 where the
+ * denominator is 0. */
+static double petsc_div(double a, double b) { return b == 0.0 ? 0.0 : a / b; }
+ORC_API void orc_pointwise_divide(long n, const double *x, const double *y, double *w) {
+    for (long i = 0; i < n; i++) w[i] = petsc_div(x[i], y[i]);
+}
+
 /* Filter::FilterProject for filterType 0/1 (Filter.cc:60-117); type 2 is
  * orc_pdef_apply + clamp, driven from the caller. */
 ORC_API void orc_filter_project(orc_filter_t *f, int type, const double *x, double *xTilde, double *xPhys, int proj,
@@ -1328,7 +1335,7 @@ ORC_API void orc_filter_project(orc_filter_t *f, int type, const double *x, doub
     long n = f->H->nrow;
     if (type == 1) {
         csr_spmv(f->H, x, xTilde);
-        for (long i = 0; i < n; i++) xTilde[i] = xTilde[i] / f->Hs[i];
+        for (long i = 0; i < n; i++) xTilde[i] = petsc_div(xTilde[i], f->Hs[i]);
     } else {
         memcpy(xTilde, x, sizeof(double) * (size_t)n);
     }
@@ -1347,10 +1354,10 @@ ORC_API void orc_filter_gradient(orc_filter_t *f, int type, const double *x, con
     if (type == 0) {
         for (long i = 0; i < n; i++) tmp[i] = df[i] * x[i];
         csr_spmv(f->H, tmp, df);
-        for (long i = 0; i < n; i++) tmp[i] = df[i] / f->Hs[i];
-        for (long i = 0; i < n; i++) df[i] = tmp[i] / x[i];
+        for (long i = 0; i < n; i++) tmp[i] = petsc_div(df[i], f->Hs[i]);
+        for (long i = 0; i < n; i++) df[i] = petsc_div(tmp[i], x[i]);
     } else if (type == 1) {
-        for (long i = 0; i < n; i++) tmp[i] = df[i] / f->Hs[i];
+        for (long i = 0; i < n; i++) tmp[i] = petsc_div(df[i], f->Hs[i]);
         csr_spmv(f->H, tmp, df);
     }
     free(tmp);

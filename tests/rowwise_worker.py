@@ -259,8 +259,8 @@ def cone_filter(expect, res):
             assert f.last_kernel() == want[conn], "ElemConn %d: kernel %d ran for Hs, expected %d" % (conn, f.last_kernel(), want[conn])
             t = "r%g_t%d" % (rfac, ftype)
             res[t + "_conn"], res[t + "_hs"] = np.asarray([conn]), host(f.Hs())
-            for kind in rw.GENERATORS:
-                x = rw.design(kind, ex, ey, ez, 4)
+            for kind in rw.GENERATORS + rw.FILTER_ZERO_KINDS:
+                x = rw.filter_design(kind, ex, ey, ez, 4)
                 xt, xp = grid.elem_vec(), grid.elem_vec()
                 f.FilterProject(dev(x), xt, xp)
                 if ftype == 1:

@@ -45,7 +45,8 @@ bounds come from the operation counts and the oracle's own CPU figures in tests/
         coarsest level, step 20 zero (one-launch run) / non-zero    512    1.0 / 1.6
     restrict / prolong_add (every level pair)       64 / 64    4.1 / 2.9
     dfdx on a converged state (rtol 1e-5)              128    2.2
-    cone filter, Hs / forward / gradients, the same for the tiled, z-multi, wide, ring and generic kernels
+    cone filter, Hs / forward / gradients, the same for the tiled, z-multi, wide, ring and generic kernels (the two designs with
+    exact zeros, rw.FILTER_ZERO_KINDS, included: they leave the figures where they were)
         ElemConn 1                                       64    0.02 / 0.06 / 0.04
         ElemConn 2                                      256    0.24 / 0.35 / 0.17
         ElemConn 5                                     4096    0.92 / 1.7 / 0.61
@@ -413,7 +414,9 @@ FILTER_FORMS = {
 
 @pytest.mark.parametrize("form", list(FILTER_FORMS))
 def test_cone_filter_rowwise(tmp_path, orc, arb, form):
-    """forward and gradients, types 0 and 1, rfac 1.5, 2.56 (tiled), 5.12 (wide), 10.24 (streamed ring), on the 0/1 designs"""
+    """forward and gradients, types 0 and 1, rfac 1.5, 2.56 (tiled), 5.12 (wide), 10.24 (streamed ring), on the 0/1 designs and on the
+    two with exact zeros (rw.FILTER_ZERO_KINDS): there the sensitivity filter's rows with x_i = 0 must be exactly 0.0 -- PETSc's
+    quotient, which the arbiter forms too -- and every other row keeps its bound"""
     env, expect = FILTER_FORMS[form]
     out = str(tmp_path / "out.npz")
     e = dict(os.environ)
@@ -437,8 +440,11 @@ def test_cone_filter_rowwise(tmp_path, orc, arb, form):
             w = {"dims": (ex, ey, ez), "dof": 0}
             lab = "filter %s type %d rfac %g ElemConn %d " % (form, ftype, rfac, af.conn)
             note("filter " + form, "Hs conn %d" % af.conn, rw.assert_rowwise(d[t + "_hs"], af.hs(), cone.M(np.ones(ex * ey * ez)), c, dict(w, label=lab + "Hs")), c)
-            for kind in rw.GENERATORS:
-                x = rw.design(kind, ex, ey, ez, 4)
+            for kind in rw.GENERATORS + rw.FILTER_ZERO_KINDS:
+                x = rw.filter_design(kind, ex, ey, ez, 4)
+                if kind in rw.FILTER_ZERO_KINDS and ftype == 0:
+                    got0 = d["%s_%s_df" % (t, kind)][x == 0]
+                    assert got0.size and (got0 == 0).all() and not np.signbit(got0).any(), lab + kind + ": a row with x = 0 is not 0.0"
                 xta, ga = cached(("fref", rfac, ftype, kind), lambda: (af.project(ftype, ld(x))[0], None))
                 ga = cached(("gref", rfac, ftype, kind), lambda: af.gradient(ftype, ld(x), xta, ld(df0)))
                 note("filter " + form, "forward conn %d" % af.conn,

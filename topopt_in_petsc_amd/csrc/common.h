@@ -362,9 +362,13 @@ __global__ __launch_bounds__(BLK) void k_pw_mult(double *__restrict__ y, const d
 __global__ __launch_bounds__(BLK) void k_axpby(double *__restrict__ y, double a, const double *__restrict__ x, double b, long n) {
     for (long i = blockIdx.x * (long)BLK + threadIdx.x; i < n; i += (long)gridDim.x * BLK) y[i] = a * x[i] + b * y[i];
 }
+// PETSc's VecPointwiseDivide: the quotient, and 0 where the denominator is 0 (+0.0 or -0.0).  The division is the one the
+// callers had, so a non-zero denominator keeps its bits; every quotient of the filter (Filter.cc:70, :175-176, :184) goes
+// through this -- a void element at x = Xmin = 0 leaves the sensitivity filter with 0, not with inf or NaN.
+__host__ __device__ __forceinline__ double petsc_div(double a, double b) { return b == 0.0 ? 0.0 : a / b; }
 __global__ __launch_bounds__(BLK) void k_pw_div(double *__restrict__ w, const double *__restrict__ x,
                                                 const double *__restrict__ y, long n) {
-    for (long i = blockIdx.x * (long)BLK + threadIdx.x; i < n; i += (long)gridDim.x * BLK) w[i] = x[i] / y[i];
+    for (long i = blockIdx.x * (long)BLK + threadIdx.x; i < n; i += (long)gridDim.x * BLK) w[i] = petsc_div(x[i], y[i]);
 }
 __global__ __launch_bounds__(BLK) void k_dot(const double *__restrict__ a, const double *__restrict__ b, long n,
                                              double *__restrict__ partials, unsigned *ticket, double *__restrict__ out) {

@@ -8,7 +8,8 @@
 // domain boundary exactly like the reference's k2/j2/i2 loops (:417-420).
 #pragma once
 
-// out_i = (sum_j w_ij in_j) [/ d1_i] [/ d2_i];  in = ghosted copy (conn layers below/above the own ones)
+// out_i = (sum_j w_ij in_j) [/ d1_i] [/ d2_i];  in = ghosted copy (conn layers below/above the own ones); every quotient by
+// PETSc's rule, 0 where the denominator is 0 (petsc_div, common.h), in all five forms of the kernel
 __global__ __launch_bounds__(BLK) void k_conv_filter(int ex, int ey, int ez_own, int conn, int e0z, int ez_glob,
                                                      const double *__restrict__ xg, const double *__restrict__ wtab,
                                                      double *__restrict__ out, const double *__restrict__ d1,
@@ -28,8 +29,8 @@ __global__ __launch_bounds__(BLK) void k_conv_filter(int ex, int ey, int ez_own,
             const double *__restrict__ wr = wtab + ((k2 - k + conn) * w1 + (j2 - j + conn)) * w1 + (conn - i);
             for (int i2 = ilo; i2 <= ihi; i2++) s = fma(wr[i2], row[i2], s);
         }
-    if (d1) s = s / d1[t];
-    if (d2) s = s / d2[t];
+    if (d1) s = petsc_div(s, d1[t]);
+    if (d2) s = petsc_div(s, d2[t]);
     out[t] = s;
 }
 // The same filter as an LDS-tiled stencil: a 32 x 4 x 2 block of elements stages its (32+2C) x (4+2C) x (2+2C)
@@ -63,8 +64,8 @@ __global__ __launch_bounds__(256) void k_conv_filter_tiled(int ex, int ey, int e
             for (int di = 0; di < W1; di++)
                 s = fma(wtab[(dk * W1 + dj) * W1 + di], s_x[((tz + dk) * SY + (ty + dj)) * SX + tx + di], s);
     const long t = (long)i + (long)ex * (j + (long)ey * k);
-    if (d1) s = s / d1[t];
-    if (d2) s = s / d2[t];
+    if (d1) s = petsc_div(s, d1[t]);
+    if (d2) s = petsc_div(s, d2[t]);
     out[t] = s;
 }
 // Round 6, small radii (ElemConn 1, 2; counters: the one-output form above is LDS-issue bound -- one ds_read per fma): NO outputs
@@ -136,8 +137,8 @@ __global__ __launch_bounds__(256) void k_conv_filter_zmulti(int ex, int ey, int 
         if (k >= ez_own) break;
         const long t = (long)i + (long)ex * (j + (long)ey * k);
         double sres = acc[o];
-        if (d1) sres = sres / d1[t];
-        if (d2) sres = sres / d2[t];
+        if (d1) sres = petsc_div(sres, d1[t]);
+        if (d2) sres = petsc_div(sres, d2[t]);
         out[t] = sres;
     }
 }
@@ -188,12 +189,12 @@ __global__ __launch_bounds__(8 * TYE * TZE) void k_conv_filter_wide(int ex, int 
         if (i >= ex) break;
         const long t = (long)i + (long)ex * (j + (long)ey * k);
         double s = acc[o];
-        if (d1) s = s / d1[t];
-        if (d2) s = s / d2[t];
+        if (d1) s = petsc_div(s, d1[t]);
+        if (d2) s = petsc_div(s, d2[t]);
         out[t] = s;
     }
 }
-// ghosted input: mode 0: a, 1: a / b, 2: a * b
+// ghosted input: mode 0: a, 1: a / b (petsc_div), 2: a * b
 // Radii beyond ElemConn 8, up to 24 (round 4; the reference's absolute default rmin = 0.08 gives 10 at 128^3 and on C3, 20 on C5): the
 // (32 + 2C) x (T + 2C) x (T + 2C) neighbourhood of a block no longer fits the LDS, so the z direction is STREAMED: a block of
 // 32 x 16 x 4 elements (one wave per z layer, eight x-outputs per thread) stages one (32 + 2C) x (16 + 2C) plane at a time,
@@ -258,8 +259,8 @@ __global__ __launch_bounds__(256) void k_conv_filter_zring(int ex, int ey, int e
         if (i >= ex) break;
         const long t = (long)i + (long)ex * (j + (long)ey * k);
         double s = acc[o];
-        if (d1) s = s / d1[t];
-        if (d2) s = s / d2[t];
+        if (d1) s = petsc_div(s, d1[t]);
+        if (d2) s = petsc_div(s, d2[t]);
         out[t] = s;
     }
 }
@@ -267,7 +268,7 @@ __global__ __launch_bounds__(256) void k_conv_filter_zring(int ex, int ey, int e
 __global__ __launch_bounds__(BLK) void k_fill_pw(double *__restrict__ y, const double *__restrict__ a,
                                                  const double *__restrict__ b, int mode, long n) {
     for (long i = blockIdx.x * (long)BLK + threadIdx.x; i < n; i += (long)gridDim.x * BLK)
-        y[i] = mode == 0 ? a[i] : (mode == 1 ? a[i] / b[i] : a[i] * b[i]);
+        y[i] = mode == 0 ? a[i] : (mode == 1 ? petsc_div(a[i], b[i]) : a[i] * b[i]);
 }
 // Heaviside projection and its derivative (Filter.h:80-88)
 __global__ __launch_bounds__(BLK) void k_heaviside(double *__restrict__ y, const double *__restrict__ x, double beta,
