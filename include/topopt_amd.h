@@ -629,6 +629,9 @@ int tp_overhang_forward(tp_overhang *ov, const double *x, double *xi);   /* TP_E
 /* g[v] <- J^T g[v], v < nvec, 1 <= nvec <= 8; TP_ERR_ARG without a forward call on this handle before it */
 int tp_overhang_adjoint(tp_overhang *ov, int nvec, double *const *g);
 int tp_overhang_last_chunk(const tp_overhang *ov);              /* layers per launch of the last sweep */
+/* copies of the coefficients the last forward call stored for the transpose, [dev, own elements] each, any of them may be
+ * NULL: a, w, p of the formulas above (layer 0: a = 1, w = 0).  Read-only; TP_ERR_ARG before a forward call. */
+int tp_overhang_get_coefficients(tp_overhang *ov, double *a, double *w, double *p);
 
 /* ---- casting (draw-direction) filter (no reference counterpart) ---- */
 /* A "cast" density c built from the blueprint density x line by line along the draw axis: a part that leaves a mould along that
@@ -654,6 +657,8 @@ int tp_casting_forward(tp_casting *c, const double *x, double *out);   /* TP_ERR
 /* g[v] <- J^T g[v], v < nvec, 1 <= nvec <= 8; TP_ERR_ARG without a forward call on this handle before it */
 int tp_casting_adjoint(tp_casting *c, int nvec, double *const *g);
 int tp_casting_last_form(const tp_casting *c);                  /* 1 walk, 2 LDS-staged x, 3 strided x walk */
+/* copy of q of the last forward call, [dev, own elements] (a sweep's first cell: 1).  Read-only; TP_ERR_ARG before a forward call. */
+int tp_casting_get_q(tp_casting *c, double *q);
 
 /* ---- passive regions: elements held at a fixed density (no reference counterpart) ---- */
 /* Labels per own element, natural order: 0 active, 1 void, 2 solid.  The optimiser works on the active elements alone, packed in

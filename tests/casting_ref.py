@@ -181,7 +181,9 @@ def name(ne):
 def check_against_reference(tp, grid, ne, draw, kind):
     """The device against the 80-bit restatement.  The bound is the double restatement's own distance d from the 80-bit one on
     the same input, times 16, with a floor of 64 * 2^-53: c absolute, the transpose relative to its maximum.  Also the sandwich,
-    monotonicity to 4 ulp and the absence of NaN on the device's output.  -> the figures"""
+    monotonicity to 4 ulp and the absence of NaN on the device's output.  Then row by row (tests/design_rowwise.py): c, the
+    stored q and the transposes, the latter against the 80-bit recursion on the device's own q.  -> the figures"""
+    from tests import design_rowwise as dr
     x, g, fl, fd, al, ad = references(ne, draw, kind)
     cf = tp.Casting(grid, draw)
     try:
@@ -191,6 +193,7 @@ def check_against_reference(tp, grid, ne, draw, kind):
         cf.Adjoint(gv)
         c_h = c.cpu().numpy()
         out_h = [v.cpu().numpy() for v in gv]
+        q_h = cf.Q().cpu().numpy()
     finally:
         cf.close()
     d_c = float(np.abs(fd["c"].astype(LD) - fl["c"]).max())
@@ -216,4 +219,9 @@ def check_against_reference(tp, grid, ne, draw, kind):
     assert mono <= 4.0
     for e, b in res:
         assert e <= b
+    case = dr.cast_case(tuple(ne), draw, kind)
+    assert np.array_equal(case["x"], x) and all(np.array_equal(a, b) for a, b in zip(case["g"], g))
+    got = dr.cast_hold(case, c_h, q_h, out_h)
+    print("    row-wise, achieved c (bound): c %.2f (%g), q %.2f (%g), transposes %.2f (%g)"
+          % (got["c"], dr.C_CAST_C, got["q"], dr.C_CAST_Q, got["adj"], dr.c_cast_adj(case["n"])))
     return res

@@ -87,16 +87,18 @@ def bounds(conn, p):
 
 
 def check_against_reference(tp, ne, h, R, kind, p, alpha=0.6, expect_kernel=None, tag=""):
-    """One mesh, one field, one exponent on cuda:0 against reference(): checks 1-5 of tests/test_gpu_localvol.py.  Every figure
-    is printed with its bound before anything is asserted.  Returns the device results."""
+    """One mesh, one field, one exponent on cuda:0 against reference(): checks 1-5 of tests/test_gpu_localvol.py, then rhobar and
+    dgdx row by row, each relative to its own value (tests/design_rowwise.py; its fields are accepted here as well).  Every
+    figure is printed with its bound before anything is asserted.  Returns the device results."""
     import torch
+    from tests import design_rowwise as dr
     dev = lambda a: torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float64))).cuda()
     grid = tp.Grid(ne[0] + 1, ne[1] + 1, ne[2] + 1, tuple(h))
     try:
         lv = tp.LocalVolume(grid, R)
         conn = stencil_width(ne, h, R)
-        rho = field(kind, ne)
-        ref = reference(rho, ne, h, R, alpha, p)
+        case = dr.lv_case(tuple(ne), tuple(h), R, kind, p, alpha)
+        rho, ref = case["rho"], case["ref"]
         b = bounds(conn, p)
         x = dev(rho)
         rb, dg, rb2 = grid.elem_vec(), grid.elem_vec(), grid.elem_vec()
@@ -133,6 +135,9 @@ def check_against_reference(tp, ne, h, R, kind, p, alpha=0.6, expect_kernel=None
         assert (g2, pn2, mx2) == (g, pn, mx)                # the forward-only call: the same values
         assert e_dg <= b["dgdx"]                                                     # 4
         assert e_eu <= b_eu                                                          # 5
-        return dict(g=g, pn=pn, mx=mx, rb=rb_h, dgdx=dg_h, cnt=cnt, kernel=kern)
+        got = dr.lv_hold(case, rb_h, dg_h, tag=tag)
+        print("    row-wise, each row relative to itself, achieved c (bound): rhobar %.2f (%g), dgdx %.2f (%g)"
+              % (got["rb"], case["c"][0], got["dgdx"], case["c"][1]), flush=True)
+        return dict(g=g, pn=pn, mx=mx, rb=rb_h, dgdx=dg_h, cnt=cnt, kernel=kern, rowwise=got)
     finally:
         grid.close()

@@ -1,12 +1,13 @@
 """Child processes of tests/test_gpu_localvol.py and tests/test_gpu_localvol_slabs.py.
 
-usage: localvol_worker.py kernel ex ey ez hx hy hz R k[,k...]       one process, cuda:0: every field and exponent of the GPU test on
+usage: localvol_worker.py kernel ex ey ez hx hy hz R k[,k...]       one process, cuda:0: every field and exponent of the GPU tests on
                                                                    one mesh against the numpy restatement, the ball sum having
                                                                    run one of the kernels k (the library latches its switches
                                                                    once per process: the parent sets them in the environment)
        localvol_worker.py slabs ex ey ez R/h                       under torch.distributed.run, every rank on cuda:0: cnt, rhobar
                                                                    and dgdx of the own layers equal the one-rank call on the
-                                                                   gathered field bit for bit, g and pn to 64 * 2^-53
+                                                                   gathered field bit for bit, g and pn to 64 * 2^-53; the one-rank
+                                                                   rhobar and dgdx are held row by row (tests/design_rowwise.py)
        localvol_worker.py toowide ex ey ez R/h                     the same launch: a stencil wider than a slab is TP_ERR_ARG"""
 import os
 import sys
@@ -17,6 +18,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from tests import design_rowwise as dr  # noqa: E402
 from tests import localvol_ref as ref  # noqa: E402
 
 ALPHA = 0.6
@@ -29,9 +31,12 @@ def kernel_mode():
     h = tuple(float(v) for v in sys.argv[5:8])
     R = float(sys.argv[8])
     expect = {int(v) for v in sys.argv[9].split(",")}
-    for kind in ("random", "checker", "half"):
-        for p in (1.0, 16.0):
-            ref.check_against_reference(tp, ne, h, R, kind, p, ALPHA, expect_kernel=expect)
+    worst = {}
+    for kind in dr.LV_FIELDS:       # the fields of the GPU test and the 0/1 designs; the check holds every row (design_rowwise)
+        for p in dr.LV_PS:
+            got = ref.check_against_reference(tp, ne, h, R, kind, p, ALPHA, expect_kernel=expect)["rowwise"]
+            worst[p] = [max(a, b) for a, b in zip(worst.get(p, (0.0, 0.0)), (got["rb"], got["dgdx"]))]
+    print("row-wise over all fields, largest achieved c: " + "; ".join("p=%g rhobar %.2f, dgdx %.2f" % (p, *worst[p]) for p in dr.LV_PS), flush=True)
     print("kernel OK", flush=True)
 
 
@@ -60,6 +65,12 @@ def slabs_mode(rank, world):
                  "equal" if torch.equal(dg, dg1[es]) else "DIFFERS", e_g, e_pn, 64 * ref.U53, "equal" if mx == mx1 else "DIFFERS"),
               flush=True)
         assert torch.equal(rb, rb1[es]) and torch.equal(dg, dg1[es]) and float(dg1.abs().max()) > 0
+        if rank == 0:      # what the slabs equal, row by row against the 80-bit restatement, each row relative to itself
+            conn = lv1.stencil_width
+            case = dict(ne=(ex, ey, ez), ref=ref.reference(rho, (ex, ey, ez), (h, h, h), R, ALPHA, p), c=dr.c_lv(conn, p),
+                        label="local volume %dx%dx%d random (seed 5) p=%g conn %d, one rank" % (ex, ey, ez, p, conn))
+            got = dr.lv_hold(case, rb1.cpu().numpy(), dg1.cpu().numpy())
+            print("rank 0 p=%g row-wise, achieved c (bound): rhobar %.2f (%g), dgdx %.2f (%g)" % (p, got["rb"], case["c"][0], got["dgdx"], case["c"][1]), flush=True)
         assert e_g <= 64 * ref.U53 and e_pn <= 64 * ref.U53 and mx == mx1
     torch.cuda.synchronize()
     grid.close()

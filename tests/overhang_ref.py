@@ -7,9 +7,13 @@ remaining axis.  P = 40, eps = 1e-4, xi0 = 0.5, Q = P + ln 5 / ln xi0.
 
     xi_0 = x_0;  l >= 1:  t = p * xi of layer l - 1,  p = xi^(P-1)
     S = t(i,r) + t(i-1,r) + t(i+1,r) + t(i,r-1) + t(i,r+1)        left to right, 0 outside the mesh
-    Xi = S^(1/Q) (0 if S = 0),  d = x - Xi,  rho = sqrt(d^2 + eps),  xi = ((x + Xi) - rho + sqrt(eps)) / 2
-    a = (1 - d/rho) / 2,  w = ((1 + d/rho) / 2) * ((P/Q) * (Xi/S)) (0 if S = 0),  p = xi^(P-1);  layer 0: a = 1, w = 0
+    Xi = S^(1/Q) (0 if S < S_MIN),  d = x - Xi,  rho = sqrt(d^2 + eps),  xi = ((x + Xi) - rho + sqrt(eps)) / 2
+    a = (1 - d/rho) / 2,  w = ((1 + d/rho) / 2) * ((P/Q) * (Xi/S)) (0 if S < S_MIN),  p = xi^(P-1);  layer 0: a = 1, w = 0
     transpose, top layer first:  lambda_l = g_l + p_l * sum_5 (w lambda)_{l+1}  (same cross, same order),  out_l = a_l lambda_l
+
+S_MIN = 2^-960 in every dtype: a support sum below it counts as no support, because Xi/S = S^(1/Q - 1) leaves float64's range
+(P = 40: S < 4e-317) long before the Jacobian entry p w does.  The 80-bit restatement applies the same floor, so that both sides
+take the same branch; the fields keep S a factor 2 away from it (tests/design_rowwise.py asserts that).
 
 Fields are flat, x fastest, then y, then z, as the library's element vectors."""
 import numpy as np
@@ -18,6 +22,7 @@ LD = np.longdouble
 U53 = 2.0 ** -53
 BUILDS = {"+y": (1, 1), "-y": (1, -1), "+z": (2, 1), "-z": (2, -1)}
 P, EPS, XI0 = 40.0, 1e-4, 0.5
+S_MIN = 2.0 ** -960
 
 
 def layers(flat, ne, build):
@@ -36,21 +41,22 @@ def _cross(t):
     return (((tp[1:-1, 1:-1] + tp[1:-1, :-2]) + tp[1:-1, 2:]) + tp[:-2, 1:-1]) + tp[2:, 1:-1]
 
 
-def forward(x, ne, build, dtype=LD, P=P, eps=EPS, xi0=XI0):
-    """-> dict(xi, Xi, a, w, p), flat; Xi of layer 0 is set to x (it has no support term)"""
+def forward(x, ne, build, dtype=LD, P=P, eps=EPS, xi0=XI0, s_min=S_MIN):
+    """-> dict(xi, Xi, S, a, w, p), flat; Xi of layer 0 is set to x (it has no support term), its S to 0.  s_min = 0 is the
+    filter without the floor (S != 0), kept for the regression test of the floor"""
     T = dtype
     P_, eps_ = T(P), T(eps)
     Q = P_ + np.log(T(5)) / np.log(T(xi0))
     invQ, PoverQ, sqeps, Pm1 = 1 / Q, P_ / Q, np.sqrt(eps_), P_ - 1
     x = np.asarray(x).astype(T)
-    out = {k: np.zeros(x.size, dtype=T) for k in ("xi", "Xi", "a", "w", "p")}
+    out = {k: np.zeros(x.size, dtype=T) for k in ("xi", "Xi", "S", "a", "w", "p")}
     X = layers(x, ne, build)
     V = {k: layers(v, ne, build) for k, v in out.items()}
     V["xi"][0], V["Xi"][0], V["a"][0], V["w"][0] = X[0], X[0], 1, 0
     V["p"][0] = X[0] ** Pm1
     for l in range(1, X.shape[0]):
         S = _cross(V["p"][l - 1] * V["xi"][l - 1])
-        nz = S != 0
+        nz = (S >= T(s_min)) & (S != 0)
         Ss = np.where(nz, S, T(1))
         Xi = np.where(nz, Ss ** invQ, T(0))
         sw = np.where(nz, PoverQ * (Xi / Ss), T(0))
@@ -58,7 +64,7 @@ def forward(x, ne, build, dtype=LD, P=P, eps=EPS, xi0=XI0):
         rho = np.sqrt(d * d + eps_)
         xi = T(0.5) * (((X[l] + Xi) - rho) + sqeps)
         q = d / rho
-        V["xi"][l], V["Xi"][l] = xi, Xi
+        V["xi"][l], V["Xi"][l], V["S"][l] = xi, Xi, S
         V["a"][l] = T(0.5) * (1 - q)
         V["w"][l] = (T(0.5) * (1 + q)) * sw
         V["p"][l] = xi ** Pm1
@@ -132,7 +138,10 @@ def dev(a):
 def check_against_reference(tp, ne, build, kind):
     """The device against the 80-bit restatement.  The bound is the double restatement's own distance d from the 80-bit one on
     the same input, times 16, with a floor of 64 * 2^-53: xi absolute, the transpose relative to its maximum.  Also the
-    sandwich property and the absence of NaN on the device's output.  -> the figures"""
+    sandwich property and the absence of NaN on the device's output.  Then row by row (tests/design_rowwise.py): xi, the stored
+    coefficients a, w, p and the transposes, the latter against the 80-bit recursion on the device's own coefficients.
+    -> the figures"""
+    from tests import design_rowwise as dr
     x, g, fl, fd, al, ad = references(ne, build, kind)
     grid = tp.Grid(ne[0] + 1, ne[1] + 1, ne[2] + 1, 1.0 / ne[1])
     try:
@@ -143,6 +152,7 @@ def check_against_reference(tp, ne, build, kind):
         ov.Adjoint(gv)
         xi_h = xi.cpu().numpy()
         out_h = [v.cpu().numpy() for v in gv]
+        coef_h = [v.cpu().numpy() for v in ov.Coefficients()]
     finally:
         grid.close()
     d_xi = float(np.abs(fd["xi"].astype(LD) - fl["xi"]).max())
@@ -166,4 +176,9 @@ def check_against_reference(tp, ne, build, kind):
     assert br <= b_xi
     for e, b in res:
         assert e <= b
+    case = dr.ov_case(tuple(ne), build, kind, 0)
+    assert np.array_equal(case["x"], x) and all(np.array_equal(a, b) for a, b in zip(case["g"], g))
+    got = dr.ov_hold(case, xi_h, *coef_h, out_h)
+    print("    row-wise, achieved c (bound): xi %.2f (%g), a %.2f, w %.2f (%g), p %.2f (%g), transposes %.2f (%g)"
+          % (got["xi"], dr.C_OV_XI, got["a"], got["w"], dr.C_OV_COEF, got["p"], dr.C_OV_POW, got["adj"], dr.c_ov_adj(case["nl"])))
     return res

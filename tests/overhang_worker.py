@@ -1,7 +1,9 @@
 """Child processes of tests/test_gpu_overhang_slabs.py, under torch.distributed.run, every rank on cuda:0.
 
-usage: overhang_worker.py slabs ex ey ez        +z and -z: xi and the transpose of two vectors on the own layers equal the one-rank
-                                                call on the whole field bit for bit, at chunk lengths 1 and 4
+usage: overhang_worker.py slabs ex ey ez        +z and -z: xi, the stored a, w, p and the transpose of two vectors on the own layers
+                                                equal the one-rank call on the whole field bit for bit, at chunk lengths 1 and 4;
+                                                the one-rank result is held row by row (tests/design_rowwise.py), so the layers
+                                                handed over at the slab borders are
        overhang_worker.py ybuild ex ey ez       a y build on more than one rank is TP_ERR_ARG from tp_overhang_create"""
 import os
 import sys
@@ -11,6 +13,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from tests import design_rowwise as dr  # noqa: E402
 from tests import overhang_ref as ref  # noqa: E402
 
 
@@ -33,9 +36,13 @@ def slabs_mode(rank, world):
             gv1, gv = [ref.dev(v) for v in g[:2]], [ref.dev(v[es]) for v in g[:2]]
             ov1.Adjoint(gv1)
             ov.Adjoint(gv)
-            same = [torch.equal(xi, xi1[es])] + [torch.equal(a, b[es]) for a, b in zip(gv, gv1)]
-            print("rank %d %s chunk %d: xi %s, transposes %s" % (rank, build, c, same[0], same[1:]), flush=True)
+            co1, co = ov1.Coefficients(), ov.Coefficients()
+            same = [torch.equal(xi, xi1[es])] + [torch.equal(a, b[es]) for a, b in zip(gv, gv1)] + [torch.equal(a, b[es]) for a, b in zip(co, co1)]
+            print("rank %d %s chunk %d: xi %s, transposes %s, a, w, p %s" % (rank, build, c, same[0], same[1:3], same[3:]), flush=True)
             assert all(same) and ov.last_chunk() == c and float(gv1[0].abs().max()) > 0
+            if rank == 0 and c == 1:      # what the slabs equal, row by row against the 80-bit restatement
+                got = dr.ov_hold(dr.ov_case(ne, build, "random", 0), xi1.cpu().numpy(), *[v.cpu().numpy() for v in co1], [v.cpu().numpy() for v in gv1])
+                print("rank 0 %s row-wise, achieved c: %s" % (build, ", ".join("%s %.2f" % kv for kv in got.items())), flush=True)
         ov.close()
         ov1.close()
     torch.cuda.synchronize()

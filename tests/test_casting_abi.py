@@ -11,7 +11,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TP_ERR_ARG = 1
 CALLS = (("tp_casting_create", 4), ("tp_casting_destroy", 1), ("tp_casting_set_params", 2), ("tp_casting_forward", 3),
-         ("tp_casting_adjoint", 3), ("tp_casting_last_form", 1))
+         ("tp_casting_adjoint", 3), ("tp_casting_last_form", 1), ("tp_casting_get_q", 2))
 
 
 def _declared_args(src, name):
@@ -22,7 +22,7 @@ def _declared_args(src, name):
 
 
 def test_header_declares_the_casting_calls_and_the_binding_has_them():
-    """the handle type and the six functions on it: seven declarations, call by call"""
+    """the handle type and the seven functions on it: eight declarations, call by call"""
     from topopt_in_petsc_amd import lib
     src = open(os.path.join(ROOT, "include", "topopt_amd.h")).read()
     assert re.search(r"typedef\s+struct\s+tp_casting\s+tp_casting\s*;", src)
@@ -68,6 +68,9 @@ def test_argument_rules_answer_before_any_launch():
     assert L.tp_casting_adjoint(cf, 2, nul) == TP_ERR_ARG
     assert L.tp_casting_adjoint(cf, 1, one) == TP_ERR_ARG                    # no forward call on this handle yet
     assert L.tp_casting_last_form(None) == 0 and L.tp_casting_last_form(cf) == 0
+    assert L.tp_casting_get_q(None, x) == TP_ERR_ARG
+    assert L.tp_casting_get_q(cf, None) == TP_ERR_ARG
+    assert L.tp_casting_get_q(cf, x) == TP_ERR_ARG                           # no forward call on this handle yet
 
 
 def test_draw_strings():
@@ -81,7 +84,7 @@ def test_draw_strings():
     for bad in ("x", "z", "+", "", "up", "+w", "x:", "x:-1", "x:0", "x:70", "z:11", "y:1.5", "+x:3", "xy:3", " +x", None, 2):
         with pytest.raises(ValueError):
             Casting.parse(bad, ne)
-    for name in ("Forward", "Adjoint", "params", "last_form"):
+    for name in ("Forward", "Adjoint", "params", "last_form", "Q"):
         assert hasattr(Casting, name)
 
 

@@ -5,7 +5,7 @@ tests/overhang_ref.py, whose docstring carries the formulas.
     distance d from the 80-bit one on the same input (xi absolute, the transpose relative to its maximum), times 16, floor
     64 * 2^-53.  The margin covers the device's pow and sqrt being a couple of ulps where libm's are within one; the order of the
     five-term sums is the same on both sides.
- 2. TP_OVERHANG_CHUNK = 1, 4, 8 give the same bits in xi and in the transpose (which reads the three coefficient arrays).
+ 2. TP_OVERHANG_CHUNK = 1, 2, 4, 8 give the same bits in xi and in the transpose (which reads the three coefficient arrays).
  3. Adjoint of three vectors at once equals three single-vector calls bit for bit.
  4. (J^T g) . W of the device against the central difference of the device's own Forward, h = 1e-6, relative 1e-6.
  5. The sandwich min(x, Xi) <= xi <= min(x, Xi) + sqrt(eps)/2 and the absence of NaN on the device's output (with 1).
@@ -72,7 +72,7 @@ def test_every_chunk_length_gives_the_same_bits(tp, chunk, ne, build):
         for kind in FIELDS:
             x, g = ref.references(ne, build, kind)[:2]
             res = {}
-            for c in (1, 4, 8):
+            for c in (1, 2, 4, 8):
                 chunk(c)
                 xi, gv = grid.elem_vec(), [ref.dev(v) for v in g]
                 ov.Forward(ref.dev(x), xi)
@@ -80,7 +80,7 @@ def test_every_chunk_length_gives_the_same_bits(tp, chunk, ne, build):
                 ov.Adjoint(gv)
                 assert ov.last_chunk() == c
                 res[c] = [xi] + gv
-            for c in (4, 8):
+            for c in (2, 4, 8):
                 same = [torch.equal(a, b) for a, b in zip(res[1], res[c])]
                 print("%s %s %s: chunk %d against 1: xi %s, transposes %s" % ("x".join(map(str, ne)), build, kind, c, same[0], same[1:]))
                 assert all(same)

@@ -1827,6 +1827,12 @@ class Overhang:
         """layers per launch of the last sweep (TP_OVERHANG_CHUNK)"""
         return self.L.tp_overhang_last_chunk(self.handle)
 
+    def Coefficients(self):
+        """(a, w, p) of the last Forward, own elements: copies of what the transpose reads"""
+        a, w, p = (self.grid.elem_vec() for _ in range(3))
+        _chk(self.L.tp_overhang_get_coefficients(self.handle, _ptr(a), _ptr(w), _ptr(p)), "tp_overhang_get_coefficients")
+        return a, w, p
+
 
 class Casting:
     """Casting (draw-direction) filter (tp_casting): the density of a part that leaves its mould along `draw` without an
@@ -1885,6 +1891,12 @@ class Casting:
     def last_form(self):
         """kernel form of the last sweep: 1 walk, 2 LDS-staged x draw, 3 walk on x lines (TP_CASTING_XFORM=0)"""
         return self.L.tp_casting_last_form(self.handle)
+
+    def Q(self):
+        """q of the last Forward, own elements: a copy of what the transpose reads"""
+        q = self.grid.elem_vec()
+        _chk(self.L.tp_casting_get_q(self.handle, _ptr(q)), "tp_casting_get_q")
+        return q
 
 
 class MMA:

@@ -295,6 +295,12 @@ extern "C" int tp_casting_create(tp_casting **out, tp_grid *g, int axis, int par
     return TP_OK;
 }
 extern "C" int tp_casting_last_form(const tp_casting *c) { return c ? c->last_form : 0; }
+// read-only copy of q of the last forward sweep (own elements)
+extern "C" int tp_casting_get_q(tp_casting *c, double *q) {
+    if (!c || !q || !c->have_fwd) return TP_ERR_ARG;
+    TP_HIP(hipMemcpyAsync(q, c->cq, sizeof(double) * (size_t)c->nel, hipMemcpyDeviceToDevice, c->grid->stream));
+    return TP_OK;
+}
 
 // lines and strides of the walk kernel on this rank
 static CastGeom casting_geom(const tp_casting *c) {

@@ -7,8 +7,12 @@
 // the remaining axis.  Q = P + ln 5 / ln xi0.  Forward, bottom-up:
 //   xi_0 = x_0;  l >= 1:  t = p * xi of layer l-1 with p = xi^(P-1),
 //   S = t(i,r) + t(i-1,r) + t(i+1,r) + t(i,r-1) + t(i,r+1)   (left to right; outside the mesh: 0),
-//   Xi = S^(1/Q) (0 if S = 0),  d = x - Xi,  rho = sqrt(d^2 + eps),  xi = (x + Xi - rho + sqrt(eps)) / 2,
-//   a = (1 - d/rho)/2,  w = (1 + d/rho)/2 * (P/Q) * Xi/S (0 if S = 0),  p = xi^(P-1);  layer 0: a = 1, w = 0.
+//   Xi = S^(1/Q) (0 if S < S_MIN),  d = x - Xi,  rho = sqrt(d^2 + eps),  xi = (x + Xi - rho + sqrt(eps)) / 2,
+//   a = (1 - d/rho)/2,  w = (1 + d/rho)/2 * (P/Q) * Xi/S (0 if S < S_MIN),  p = xi^(P-1);  layer 0: a = 1, w = 0.
+// S_MIN = 2^-960: a support sum below it counts as no support.  Xi / S = S^(1/Q - 1) alone leaves the exponent range long before
+// the Jacobian entry p w does (P = 40: S < 4e-317, a supporting xi near 1e-8, gives w = inf; S underflown to 0 loses the term):
+// with the floor Xi / S <= 2^960 for every admissible Q >= 1, and p of the supporting cell stays normal.  The price is a jump of
+// S_MIN^(1/Q) in Xi, 2e-8 at the defaults; S >= S_MIN keeps its bits.
 // Transpose, top-down, in place:  lambda_l = g_l + p_l * sum_5 (w lambda)_{l+1} over the same cross in the same order,
 //   out_l = a_l lambda_l  (top layer: the sum is 0).  A gather: no atomics, no pow.
 //
@@ -21,6 +25,7 @@
 constexpr int OV_TX = 32, OV_TR = 8;  // own tile: x (the unit-stride lane direction) by the other in-plane axis
 constexpr int OV_MAXVEC = 8;
 constexpr int OV_LDS_CAP = 65536;     // bytes of LDS one transpose launch may ask for (the static limit; no attribute to raise)
+constexpr double OV_S_MIN = 0x1p-960; // support sums below this count as none (head of the file)
 
 struct OvPar {
     double Pm1, invQ, PoverQ, eps, sqeps;
@@ -40,7 +45,7 @@ __device__ __forceinline__ void ov_cell_fwd(double x, double t0, double t1, doub
 #pragma clang fp contract(off)
     const double S = (((t0 + t1) + t2) + t3) + t4;
     double Xi = 0.0, sw = 0.0;
-    if (S != 0.0) {
+    if (S >= OV_S_MIN) {
         Xi = pow(S, par.invQ);
         sw = par.PoverQ * (Xi / S);
     }
@@ -257,6 +262,15 @@ extern "C" int tp_overhang_create(tp_overhang **out, tp_grid *g, int axis, int s
     return TP_OK;
 }
 extern "C" int tp_overhang_last_chunk(const tp_overhang *ov) { return ov ? ov->last_chunk : 0; }
+// read-only copies of the coefficients the last forward sweep left for the transpose (own elements); each may be NULL
+extern "C" int tp_overhang_get_coefficients(tp_overhang *ov, double *a, double *w, double *p) {
+    if (!ov || !ov->have_fwd) return TP_ERR_ARG;
+    const size_t nb = sizeof(double) * (size_t)ov->nel;
+    if (a) TP_HIP(hipMemcpyAsync(a, ov->ca, nb, hipMemcpyDeviceToDevice, ov->grid->stream));
+    if (w) TP_HIP(hipMemcpyAsync(w, ov->cw, nb, hipMemcpyDeviceToDevice, ov->grid->stream));
+    if (p) TP_HIP(hipMemcpyAsync(p, ov->cp, nb, hipMemcpyDeviceToDevice, ov->grid->stream));
+    return TP_OK;
+}
 
 template <int C>
 static int overhang_sweep_fwd(tp_overhang *ov, const double *x, double *xi, bool first) {

@@ -208,12 +208,14 @@ SYMBOLS = {
     "tp_overhang_forward": (_i, [_vp, _vp, _vp]),
     "tp_overhang_adjoint": (_i, [_vp, _i, C.POINTER(_vp)]),
     "tp_overhang_last_chunk": (_i, [_vp]),
+    "tp_overhang_get_coefficients": (_i, [_vp, _vp, _vp, _vp]),
     "tp_casting_create": (_i, [C.POINTER(_vp), _vp, _i, _i]),
     "tp_casting_destroy": (_i, [_vp]),
     "tp_casting_set_params": (_i, [_vp, _d]),
     "tp_casting_forward": (_i, [_vp, _vp, _vp]),
     "tp_casting_adjoint": (_i, [_vp, _i, C.POINTER(_vp)]),
     "tp_casting_last_form": (_i, [_vp]),
+    "tp_casting_get_q": (_i, [_vp, _vp]),
     "tp_localvol_constraint": (_i, [_vp, _vp, _d, _d, C.POINTER(_d), C.POINTER(_d), C.POINTER(_d), _vp, _vp]),
     "tp_lengthscale_create": (_i, [C.POINTER(_vp), _vp]),
     "tp_lengthscale_destroy": (_i, [_vp]),
