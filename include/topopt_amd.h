@@ -684,6 +684,38 @@ int tp_passive_zero(tp_passive *p, int nvec, double *const *rows);
 int tp_passive_gather(tp_passive *p, int nvec, const double *const *full, double *const *packed);
 int tp_passive_scatter(tp_passive *p, int nvec, const double *const *packed, double *const *full);
 
+/* ---- design-variable linking: mirror symmetry, pattern repetition, extrusion (no reference counterpart) ---- */
+/* One mode per axis (x, y, z) of the own elements, ne of them along the axis:
+ *   0 none     r(i) = i                 nr = ne           preimage of I: {I}
+ *   1 mirror   r(i) = min(i, ne-1-i)    nr = (ne+1)/2     {I, ne-1-I}, one member where they coincide
+ *   2 repeat   r(i) = i mod (ne/cells)  nr = ne/cells     {I, I+nr, .., I+(cells-1) nr}; cells >= 2 divides ne
+ *   3 extrude  r(i) = 0                 nr = 1            {0 .. ne-1}
+ * The optimiser works on the reduced vector, the box nr_x x nr_y x nr_z in natural order (x fastest); the filter and the physics
+ * work on the full fields.  The orbit of a reduced variable is the product of its three preimages.  cells[a] is read for mode 2 only.
+ * The three per-iteration calls take host arrays of nvec [dev] pointers, 1 <= nvec <= TP_LINK_MAXVEC, and handle all of them in ONE
+ * launch:
+ *   expand  full[v][e] = red[v][r(e)]
+ *   fold    red[v][j]  = the sum of full[v][e] over orbit(j): sequential in ascending natural element order (z outer, then y,
+ *           then x), started with the first member's value, plain IEEE adds -- the same bits from every kernel form and run
+ *   pick    red[v][j]  = full[v][first member of orbit(j)]
+ * set_form chooses fold's kernel for this handle: 0 the measured rule, 1 one reduced variable per thread, 2 x rows staged through
+ * LDS where that applies (an x mode other than none, at most 512 elements along x; form 1 otherwise); last_form reports the form
+ * of the last fold (0 before the first, and for NULL).
+ * TP_ERR_ARG, before the handle or the grid's stream is used, for a NULL handle, array or vector, nvec outside 1..TP_LINK_MAXVEC,
+ * any source pointer equal to any destination pointer, a mode outside 0..3, repeat with fewer than 2 cells or a cell count that
+ * does not divide ne, a form outside 0..2, and a z mode other than none on a grid of more than one rank (with x and y links every
+ * orbit lies inside a slab: a rank's reduced vector is nr_x x nr_y x ez_own and nothing is communicated). */
+#define TP_LINK_MAXVEC 12
+typedef struct tp_link tp_link;
+int tp_link_create(tp_link **l, tp_grid *g, const int mode[3], const int cells[3]);
+int tp_link_destroy(tp_link *l);                                /* NULL: TP_OK */
+int tp_link_counts(const tp_link *l, long *n_reduced_own, long nr[3]);   /* each may be NULL */
+int tp_link_expand(tp_link *l, int nvec, const double *const *red, double *const *full);
+int tp_link_fold(tp_link *l, int nvec, const double *const *full, double *const *red);
+int tp_link_pick(tp_link *l, int nvec, const double *const *full, double *const *red);
+int tp_link_set_form(tp_link *l, int form);
+int tp_link_last_form(const tp_link *l);
+
 /* ---- robust design: eroded / nominal / dilated projections of one filtered field (no reference counterpart) ---- */
 /* project  out[k][i] = H(xTilde[i]; beta, eta[k]) for k < nproj in ONE launch that reads xTilde once; each field has the bits of
  *          tp_filter_project's projection at its threshold.  With p a void element receives 0.0 and a solid one 1.0 in every field

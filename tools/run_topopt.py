@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """End-to-end run of the reference's optimisation loop on the MI355X path.
-usage: run_topopt.py [--physics elasticity|heat|thermoelastic [--alpha A] [--thermal uniform:DT] [--t-ref T] [--thermal-penal P]] [--loadcase top[:weight]]... [--stress-limit L [--stress-p P] [--stress-q q]] [--local-volume ALPHA:R] [--overhang +z|-z|+y|-y] [--casting DRAW [--casting-eps E]] [--self-weight bx,by,bz[:xlow] [--no-point-load]] [--length-scale both|solid|void[:C]] [--frequency-limit L[:nev]] [--load cantilever|axial] [--buckling-limit L[:nev]] [--passive solid|void:box|sphere|cylinder:numbers]... [--robust ETA_E,ETA_N,ETA_D[:every]] ex ey ez nlvls n_iter [filter [nsmooth ncoarse]]
+usage: run_topopt.py [--physics elasticity|heat|thermoelastic [--alpha A] [--thermal uniform:DT] [--t-ref T] [--thermal-penal P]] [--loadcase top[:weight]]... [--stress-limit L [--stress-p P] [--stress-q q]] [--local-volume ALPHA:R] [--overhang +z|-z|+y|-y] [--casting DRAW [--casting-eps E]] [--self-weight bx,by,bz[:xlow] [--no-point-load]] [--length-scale both|solid|void[:C]] [--frequency-limit L[:nev]] [--load cantilever|axial] [--buckling-limit L[:nev]] [--passive solid|void:box|sphere|cylinder:numbers]... [--robust ETA_E,ETA_N,ETA_D[:every]] [--link AXIS:MODE[:CELLS]]... ex ey ez nlvls n_iter [filter [nsmooth ncoarse]]
 (e.g. 128 128 128 5 20 1 2 45: the cycle of bench.py; --loadcase top:0.5 adds the line load on the upper edge as a second load
 case of weight 0.5 -- the objective becomes the weighted sum of the cases' compliances; --stress-limit L holds the von Mises
 p-norm of load case 0 below L as a second constraint, exponent --stress-p (8), stress relaxation x^q with --stress-q (0.5); --local-volume ALPHA:R holds the mean density in a ball of
@@ -27,7 +27,9 @@ x = 0 and a uniform source, conductivity 1e-3 + xPhys^3 (1 - 1e-3), the thermal 
 only, none of the other options; --physics thermoelastic --alpha A runs the cantilever under its point load plus the thermal
 expansion of a temperature field: by default the heat-sink problem's, solved on the same grid, with --thermal
 uniform:DT a uniform rise DT above the reference temperature --t-ref (0); --thermal-penal is the exponent of the thermal stress
-coefficient's interpolation (the stiffness's) -- with --passive only, none of the other options)"""
+coefficient's interpolation (the stiffness's) -- with --passive only, none of the other options; --link AXIS:MODE[:CELLS] links
+design variables along an axis: x:mirror, y:repeat:4, z:extrude, one per axis -- MMA works on one variable per orbit
+and the design is exactly symmetric, periodic or constant along the axis; not together with --passive)"""
 import os
 import sys
 
@@ -124,6 +126,7 @@ for v in _option("--passive", ": solid|void:box|sphere|cylinder:numbers"):
         shapes.append((kind, form, tuple([a if a in ("x", "y", "z") else int(a) for a in axis] + [float(t) for t in nums])))
     except ValueError:
         sys.exit("--passive needs KIND:SHAPE:numbers, e.g. solid:box:1.9,2,0,1,0,0.1, got %r" % v)
+links = _option("--link", ": AXIS:MODE[:CELLS], e.g. y:mirror, x:repeat:4, z:extrude")
 robust_arg, robust = _last("--robust"), {}
 if robust_arg is not None:
     etas, _, every = robust_arg.partition(":")
@@ -155,7 +158,7 @@ ex, ey, ez, nlv, nit = [int(v) for v in sys.argv[1:6]]
 flt = int(sys.argv[6]) if len(sys.argv) > 6 else 1
 h = 1.0 / ey
 opt = tp.TopOpt(nxyz=(ex + 1, ey + 1, ez + 1), xc=(0, ex * h, 0, 1, 0, ez * h), nlvls=nlv, rmin=2.56 * h, filter=flt,
-                loadcases=loadcases or None, **stress, **local, overhang=overhang, **casting, **body, **length, **frequency, load=load_arg, **buckling, passive=shapes or None, **robust, physics=physics, **thermo,
+                loadcases=loadcases or None, **stress, **local, overhang=overhang, **casting, **body, **length, **frequency, load=load_arg, **buckling, passive=shapes or None, link=links or None, **robust, physics=physics, **thermo,
                 solver=tp.SolverOptions(nlvls=nlv, **(dict(nsmooth=int(sys.argv[7]), ncoarse=int(sys.argv[8])) if len(sys.argv) > 8 else {})))
 print("# %dx%dx%d elements, %d DOF, %d MG levels, filter %d, rmin %.4f" % (ex, ey, ez, (1 if physics == "heat" else 3) * (ex + 1) * (ey + 1) * (ez + 1), nlv, flt, 2.56 * h))
 for it in range(nit):
@@ -190,6 +193,8 @@ for it in range(nit):
         xp = opt.xPhys.cpu().numpy()
         print("Passive:       %d active of %d elements | xPhys exact on the own void elements: %s, solid: %s"
               % (r["n_active"], ex * ey * ez, bool((xp[lab == 1] == 0.0).all()), bool((xp[lab == 2] == 1.0).all())), flush=True)
+    if "n_reduced" in r:
+        print("Link:          %s | %d reduced of %d design variables" % (" ".join(links), r["n_reduced"], ex * ey * ez), flush=True)
     if "vol_real" in r:
         print("Robust:        eta: %s, beta: %g | volume eroded / nominal / dilated: %s, dilated target: %f"
               % (",".join("%g" % v for v in opt.robust), opt.beta, " ".join("%f" % v for v in r["vol_real"]), r["vol_dilated_target"]), flush=True)

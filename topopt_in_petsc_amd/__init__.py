@@ -7,5 +7,5 @@ and torch.distributed for the z-slab halo exchange.
 """
 from .lib import load_library, LibraryMissing  # noqa: F401
 from .partition import SlabPartition  # noqa: F401
-from .api import Grid, LinearElasticity, HeatConduction, Filter, LocalVolume, LengthScale, Overhang, Casting, Passive, passive_labels, Robust, MMA, SolverOptions, TopOptError, device_bytes_live  # noqa: F401
+from .api import Grid, LinearElasticity, HeatConduction, Filter, LocalVolume, LengthScale, Overhang, Casting, Passive, passive_labels, Link, parse_link, Robust, MMA, SolverOptions, TopOptError, device_bytes_live  # noqa: F401
 from .driver import TopOpt  # noqa: F401

@@ -1743,6 +1743,124 @@ class Passive:
         return full
 
 
+LINK_MODES = {"none": 0, "mirror": 1, "repeat": 2, "extrude": 3}
+
+
+def parse_link(spec, ne=None):
+    """-> (modes, cells), two 3-tuples for tp_link_create (mode 0 none, 1 mirror, 2 repeat, 3 extrude; cells 0 but for repeat).
+    spec: a dict {"x": "mirror", "y": ("repeat", 4), "z": "extrude"}, or strings "x:mirror", "y:repeat:4", "z:extrude" -- one, or a
+    list of them.  Axes left out are not linked.  ne: the element counts (x, y, z) the cell counts must divide (None: not checked).
+    ValueError for an axis given twice, an unknown axis or mode, a cell count below 2 or one that does not divide its axis."""
+    items = []
+    if isinstance(spec, dict):
+        for axis, how in spec.items():
+            if isinstance(how, str):
+                items.append((axis,) + tuple(how.split(":")))
+            elif isinstance(how, (tuple, list)) and how:
+                items.append((axis,) + tuple(how))
+            else:
+                raise ValueError("link: %r: need a mode name or (\"repeat\", cells), got %r" % (axis, how))
+    else:
+        if isinstance(spec, str):
+            spec = [spec]
+        if not isinstance(spec, (list, tuple)):
+            raise ValueError("link: need a dict or strings AXIS:MODE[:CELLS], got %r" % (spec,))
+        for s in spec:
+            if not isinstance(s, str):
+                raise ValueError("link: need strings AXIS:MODE[:CELLS], got %r" % (s,))
+            items.append(tuple(s.split(":")))
+    modes, cells, seen = [0, 0, 0], [0, 0, 0], set()
+    for item in items:
+        if len(item) < 2 or item[0] not in ("x", "y", "z"):
+            raise ValueError("link: need AXIS:MODE[:CELLS] with AXIS x, y or z, got %r" % (":".join(map(str, item)),))
+        a, mode = "xyz".index(item[0]), item[1]
+        if a in seen:
+            raise ValueError("link: axis %s is given twice" % item[0])
+        seen.add(a)
+        if mode not in LINK_MODES:
+            raise ValueError("link: unknown mode %r (the modes are none, mirror, repeat:CELLS, extrude)" % (mode,))
+        if len(item) != (3 if mode == "repeat" else 2):
+            raise ValueError("link: %s takes %s, got %r" % (mode, "a cell count" if mode == "repeat" else "no argument", ":".join(map(str, item))))
+        modes[a] = LINK_MODES[mode]
+        if mode == "repeat":
+            c = item[2]
+            if isinstance(c, bool) or (not isinstance(c, (int, str))) or (isinstance(c, str) and not c.isdigit()):
+                raise ValueError("link: repeat needs a whole number of cells, got %r" % (c,))
+            c = int(c)
+            if c < 2:
+                raise ValueError("link: repeat needs at least 2 cells, got %d" % c)
+            if ne is not None and ne[a] % c != 0:
+                raise ValueError("link: %d cells do not divide the %d elements along %s" % (c, ne[a], item[0]))
+            cells[a] = c
+    return tuple(modes), tuple(cells)
+
+
+class Link:
+    """Design-variable linking (tp_link): per axis none, mirror, repeat:c or extrude, and the three maps between the
+    reduced design the optimiser sees (the box nr_x x nr_y x nr_z, x fastest) and the full fields of the filter and the physics.
+    Every call takes lists of 1 to MAXVEC tensors and handles all of them in one launch.  Fold's sum has one fixed order (ascending
+    element order, the first member first), so its bits do not depend on the kernel form or the run."""
+    MAXVEC = _lib.LINK_MAXVEC
+
+    def __init__(self, grid, spec):
+        self.grid, self.L = grid, grid.L
+        part = grid.part
+        self.modes, self.cells = parse_link(spec, (part.ex, part.ey, part.ez_own))
+        self.handle = C.c_void_p()
+        _chk(self.L.tp_link_create(C.byref(self.handle), grid.handle, (C.c_int * 3)(*self.modes), (C.c_int * 3)(*self.cells)),
+             "tp_link_create")
+        grid._adopt(self)
+        self.n_reduced, self.nr = self.counts()
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.L.tp_link_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def counts(self):
+        """(own reduced variables, (nr_x, nr_y, nr_z))"""
+        n, nr = C.c_long(), (C.c_long * 3)()
+        _chk(self.L.tp_link_counts(self.handle, C.byref(n), nr), "tp_link_counts")
+        return n.value, tuple(nr)
+
+    def reduced_vec(self, value=0.0):
+        return torch.full((self.n_reduced,), value, dtype=torch.float64, device=self.grid.device)
+
+    def set_form(self, form):
+        """fold's kernel: 0 the measured rule, 1 one reduced variable per thread, 2 x rows through LDS where that applies"""
+        _chk(self.L.tp_link_set_form(self.handle, int(form)), "tp_link_set_form")
+
+    def last_form(self):
+        return self.L.tp_link_last_form(self.handle)
+
+    def _call(self, fn, name, src, n_src, dst, n_dst):
+        if len(src) != len(dst):
+            raise ValueError("Link.%s: %d source and %d destination vectors" % (name, len(src), len(dst)))
+        for t, n in [(t, n_src) for t in src] + [(t, n_dst) for t in dst]:
+            assert t.numel() == n, "Link: a vector of %d entries where %d are needed" % (t.numel(), n)
+        arr = lambda vecs: (C.c_void_p * max(len(vecs), 1))(*[_ptr(t) for t in vecs])
+        _chk(fn(self.handle, len(src), arr(src), arr(dst)), "tp_link_" + name.lower())
+        return dst
+
+    def Expand(self, reds, fulls):
+        """fulls[v][e] <- reds[v][r(e)]"""
+        return self._call(self.L.tp_link_expand, "Expand", reds, self.n_reduced, fulls, self.grid.n_own_elems)
+
+    def Fold(self, fulls, reds):
+        """reds[v][j] <- the sum of fulls[v] over the orbit of j, in ascending element order"""
+        return self._call(self.L.tp_link_fold, "Fold", fulls, self.grid.n_own_elems, reds, self.n_reduced)
+
+    def Pick(self, fulls, reds):
+        """reds[v][j] <- fulls[v] at the first member of the orbit of j"""
+        return self._call(self.L.tp_link_pick, "Pick", fulls, self.grid.n_own_elems, reds, self.n_reduced)
+
+
 class Robust:
     """Robust three-field formulation (tp_robust_project / tp_robust_chain): one filtered field projected at up to MAXPROJ
     thresholds with one beta in one launch -- the eroded, nominal and dilated designs -- and the projections' derivatives put on

@@ -1444,6 +1444,11 @@ extern "C" int tp_elasticity_last_op_form(const tp_elasticity *e, int *form4) {
 #include "passive.h"
 
 // ===========================================================================
+// design-variable linking: mirror, repeat, extrude between the reduced design and the full field
+// ===========================================================================
+#include "link.h"
+
+// ===========================================================================
 // robust design: eroded / nominal / dilated projections in one launch
 // ===========================================================================
 #include "robust.h"

@@ -16,7 +16,7 @@ import torch
 from . import mpiio
 import ctypes as C
 
-from .api import Casting, Filter, Grid, HeatConduction, LengthScale, LinearElasticity, LocalVolume, MMA, Overhang, Passive, Robust, SolverOptions, _chk, _ptr, check_body_force, check_thermal, passive_labels
+from .api import Casting, Filter, Grid, HeatConduction, LengthScale, LinearElasticity, Link, LocalVolume, MMA, Overhang, Passive, Robust, SolverOptions, _chk, _ptr, check_body_force, check_thermal, parse_link, passive_labels
 
 
 def robust_volume_target(volfrac, S_d, S_n):
@@ -147,6 +147,12 @@ class TopOpt:
     # api.passive_labels.  Void elements are held at x = Xmin, xPhys = 0, solid ones at x = Xmax, xPhys = 1; MMA works on the
     # active elements alone, packed; the volume constraint stays the mean over ALL elements (None: none, nothing changes)
     passive: object = None
+    # design-variable linking: per axis "mirror", ("repeat", cells) or "extrude" -- a dict {"y": "mirror"}, or strings
+    # "y:mirror", "x:repeat:4", "z:extrude" (one or a list).  MMA works on the reduced design (one variable per orbit); x is its
+    # expansion, so the filter and everything behind it see the full field; every gradient row is folded onto the reduced vector
+    # in one fixed summation order.  The volume constraint stays the mean over ALL elements.  Not together with passive; a z link
+    # needs nranks = 1 (None: none, nothing changes)
+    link: object = None
     # robust design: robust = (eta_e, eta_n, eta_d), strictly descending inside (0, 1).  xTilde is projected at the
     # three thresholds with the one beta: xErode, xPhys (the nominal design: output, MND and restart files carry it) and xDilate.
     # The objective is the ERODED design's compliance -- for fixed loads the worst of the three, so one solve per iteration as
@@ -278,6 +284,8 @@ class TopOpt:
             if self.length_scale_c is None:
                 self.length_scale_c = self.rmin ** 4 / min(h) ** 2
         labels = self._check_passive() if self.passive is not None else None
+        if self.link is not None:
+            self._check_link()
         self.grid = Grid(nx, ny, nz, h, rank=self.rank, nranks=self.nranks)
         so = self.solver or SolverOptions(nlvls=self.nlvls, nu=self.nu)
         self.physics = (HeatConduction if self.physics_kind == "heat" else LinearElasticity)(self.grid, so)
@@ -338,6 +346,12 @@ class TopOpt:
             pr.Impose([self.x], self.Xmin, self.Xmax)   # once: the filter sees the fixed neighbours
             new, n_mma = pr.packed_vec, self.n_active
             self.xa = self._xd = new(self._x0)
+            self._dfd, self._dgd = new(), [new() for _ in range(self.m)]
+        self.linker = None
+        if self.link is not None:   # MMA on the reduced design; x, which starts uniform, is its expansion already
+            self.linker = lk = Link(g, self.link)
+            new, n_mma = lk.reduced_vec, self.n_reduced
+            self.xr = self._xd = new(self.volfrac)
             self._dfd, self._dgd = new(), [new() for _ in range(self.m)]
         self.xmin, self.xmax, self.xold = new(), new(), new(self.volfrac if labels is None else self._x0)
         if self.aMMA is None and self.cMMA is None and self.dMMA is None:
@@ -484,6 +498,19 @@ class TopOpt:
                 raise ValueError("robust together with %s is not supported: the constraint would have to choose a realisation" % name)
         self.robust, self.eta = etas, etas[1]
         self.robust_volume_every, self.robust_report = int(self.robust_volume_every), int(self.robust_report)
+
+    def _check_link(self):
+        """linking's refusals and the global reduced count n_reduced; host arithmetic on the parameters, before any device object"""
+        if self.passive is not None:
+            raise ValueError("link together with passive regions is not supported")
+        ne = tuple(n - 1 for n in self.nxyz)
+        modes, cells = parse_link(self.link, ne)
+        if modes[2] != 0 and self.nranks > 1:
+            raise ValueError("link: a z link needs nranks = 1 (its orbits would cross the slabs), got nranks = %d" % self.nranks)
+        if self.m + 1 > Link.MAXVEC:
+            raise ValueError("link: the objective's row and %d constraint rows are more than one Fold takes (%d)" % (self.m, Link.MAXVEC))
+        nr = [n if mo == 0 else (n + 1) // 2 if mo == 1 else n // c if mo == 2 else 1 for n, mo, c in zip(ne, modes, cells)]
+        self.n_reduced = nr[0] * nr[1] * nr[2]
 
     def _check_passive(self):
         """the global label array of `passive`, checked; sets n_active (global) and the active elements' start value _x0.
@@ -656,10 +683,14 @@ class TopOpt:
             self.filt.GradientsFromTilde(self.x, lrows)
         if self.regions is not None:   # the active entries of the objective's row and every constraint's, one launch
             self.regions.Gather([self.dfdx] + self.dgdx, [self._dfd] + self._dgd)
+        if self.linker is not None:    # every row summed over the orbits of the reduced variables, one launch
+            self.linker.Fold([self.dfdx] + self.dgdx, [self._dfd] + self._dgd)
         self.mma.SetOuterMovelimit(self.Xmin, self.Xmax, self.movlim, self._xd, self.xmin, self.xmax)  # :81
         self.mma.Update(self._xd, self._dfd, gxs, self._dgd, self.xmin, self.xmax)               # :85
         if self.regions is not None:
             self.regions.Scatter([self.xa], [self.x])
+        if self.linker is not None:
+            self.linker.Expand([self.xr], [self.x])
         if self.kkt:
             kkt = self.mma.KKTresidual(self._xd, self._dfd, gxs, self._dgd, self.xmin, self.xmax)
         ch = self.mma.DesignChange(self._xd, self.xold)                                          # :89
@@ -701,6 +732,8 @@ class TopOpt:
             rec["ksp_its_thermal"], rec["ksp_its_thermal_adjoint"], rec["T_max"] = self._its_thermal, self._its_thermal_adjoint, T_max
         if self.regions is not None:
             rec["n_active"] = self.n_active
+        if self.linker is not None:
+            rec["n_reduced"] = self.n_reduced
         if self.robust is not None:   # of the design fx and gx belong to
             rec["vol_real"], rec["vol_dilated_target"] = [v / n_glob for v in S], self.vd_target
             if self.robust_report and self.itr % self.robust_report == 0:
@@ -743,7 +776,11 @@ class TopOpt:
         tag = "01" if self._flip else "00"
         g = self.grid
         xo1, xo2, U, L = g.elem_vec(), g.elem_vec(), g.elem_vec(), g.elem_vec()
-        if self.regions is None:
+        if self.linker is not None:   # the files keep their full-length layout: MMA's reduced vectors expanded
+            reduced = [self.linker.reduced_vec() for _ in range(4)]
+            self.mma.Restart(*reduced)
+            self.linker.Expand(reduced, [xo1, xo2, U, L])
+        elif self.regions is None:
             self.mma.Restart(xo1, xo2, U, L)
         else:   # the files keep their full-length layout: MMA's packed vectors into zero-filled full ones
             packed = [self.regions.packed_vec() for _ in range(4)]
@@ -775,8 +812,13 @@ class TopOpt:
         self.itr = int(itr)
         if self.regions is not None:   # the files are full length: the design on the active elements ...
             self.regions.Gather([self.x], [self.xa])
+        if self.linker is not None:    # the reduced design is the orbits' first members
+            self.linker.Pick([self.x], [self.xr])
+            self.linker.Expand([self.xr], [self.x])   # (a file of a run without link: x becomes the linked design of its first members)
         if not self.onlyLoadDesign:
             state = [self._own(xo1), self._own(xo2), self._own(U), self._own(L)]
+            if self.linker is not None:
+                state = self.linker.Pick(state, [self.linker.reduced_vec() for _ in range(4)])
             if self.regions is not None:   # ... and MMA's vectors
                 state = self.regions.Gather(state, [self.regions.packed_vec() for _ in range(4)])
             self.mma.SetRestart(self.itr, *state)

@@ -229,6 +229,14 @@ SYMBOLS = {
     "tp_passive_zero": (_i, [_vp, _i, C.POINTER(_vp)]),
     "tp_passive_gather": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp)]),
     "tp_passive_scatter": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp)]),
+    "tp_link_create": (_i, [C.POINTER(_vp), _vp, C.POINTER(_i), C.POINTER(_i)]),
+    "tp_link_destroy": (_i, [_vp]),
+    "tp_link_counts": (_i, [_vp, C.POINTER(_l), C.POINTER(_l)]),
+    "tp_link_expand": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp)]),
+    "tp_link_fold": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp)]),
+    "tp_link_pick": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp)]),
+    "tp_link_set_form": (_i, [_vp, _i]),
+    "tp_link_last_form": (_i, [_vp]),
     "tp_robust_project": (_i, [_vp, _vp, _d, _i, C.POINTER(_d), C.POINTER(_vp), _vp, C.POINTER(_d)]),
     "tp_robust_chain": (_i, [_vp, _vp, _d, _i, C.POINTER(_vp), C.POINTER(_d), _vp]),
     "tp_conduction_create": (_i, [C.POINTER(_vp), _vp, C.POINTER(SolverOpts)]),
@@ -260,7 +268,8 @@ SYMBOLS = {
 ABI_VERSION = 4   # TP_ABI_VERSION of include/topopt_amd.h
 MAX_CASES = 8     # TP_MAX_CASES: load cases of one tp_elasticity_response call
 PASSIVE_MAXVEC = 12   # TP_PASSIVE_MAXVEC: vectors of one tp_passive_impose / zero / gather / scatter call
-ROBUST_MAXPROJ = 3    # TP_ROBUST_MAXPROJ: fields of one tp_robust_project call, distinct thresholds of one tp_robust_chain call
+LINK_MAXVEC = 12      # TP_LINK_MAXVEC: vectors of one tp_link_expand / fold / pick call
+ROBUST_MAXPROJ = 3   # TP_ROBUST_MAXPROJ: fields of one tp_robust_project call, distinct thresholds of one tp_robust_chain call
 ROBUST_MAXROWS = 8    # TP_ROBUST_MAXROWS: rows of one tp_robust_chain call
 
 
