@@ -428,6 +428,9 @@ int tp_elasticity_precond(tp_elasticity *e, const double *r, double *z); /* one 
 /* ksp_mode 1 level by level (tests): z = M^-1 r with PCJACOBI (pc 0) or PCSOR (pc 1) on a level; the level's left-
  * preconditioned GMRES(m) for at most `its` iterations on x (rtol < 0: no convergence test, as PCMG runs its smoothers) */
 int tp_elasticity_level_pc(tp_elasticity *e, int level, int pc, const double *r, double *z);
+/* one in-place Gauss-Seidel sweep of PCSOR on x, from the iterate x holds: forward (backward == 0) or backward.  Forward from
+ * zero, then backward, is tp_elasticity_level_pc(pc 1) launch for launch.  TP_ERR_STATE outside ksp_mode 1. */
+int tp_elasticity_level_gs(tp_elasticity *e, int level, int backward, const double *b, double *x);
 int tp_elasticity_level_gmres(tp_elasticity *e, int level, int pc, int m, int its, double rtol, const double *b, double *x,
                               int zero_guess, int *its_done);
 /* k Chebyshev-Jacobi steps on a level (the fused operator+update kernel): x <- smooth(b, x) */

@@ -1123,6 +1123,11 @@ class LinearElasticity:
         _chk(self.L.tp_elasticity_level_pc(self.handle, l, pc, _ptr(r), _ptr(z)), "tp_elasticity_level_pc")
         return z
 
+    def level_gs(self, l, backward, b, x):
+        """ksp_mode 1: one Gauss-Seidel sweep of PCSOR on level l, in place on x from the iterate it holds (forward or backward)"""
+        _chk(self.L.tp_elasticity_level_gs(self.handle, l, int(backward), _ptr(b), _ptr(x)), "tp_elasticity_level_gs")
+        return x
+
     def level_gmres(self, l, pc, m, its, b, x, zero_guess=False, rtol=-1.0):
         """ksp_mode 1: the level's left-preconditioned GMRES(m), at most `its` iterations (rtol < 0: no test)"""
         import ctypes

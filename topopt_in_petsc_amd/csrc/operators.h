@@ -61,6 +61,8 @@ struct MatfreeOp {
                 if ((m >> r) & 1u) y[r] = u[n * DOF + r];
         }
     }
+    // dof r of node n is a Dirichlet row (Gauss-Seidel sweeps, refksp.h)
+    __device__ inline bool clamped(long n, int r) const { return mask && ((mask[n] >> r) & 1u); }
     // the node's own DOF x DOF block of N K N + (I - N), row major (Gauss-Seidel sweeps, refksp.h)
     __device__ inline void diag_block(long n, int i, int j, int k, double D[DOF * DOF]) const {
         constexpr int ED = 8 * DOF;
@@ -177,6 +179,7 @@ struct DiaOp {
             }
         }
     }
+    __device__ inline bool clamped(long, int) const { return false; }  // (a Galerkin level keeps no identity rows)
     __device__ inline void diag_block(long n, int, int, int, double D[DOF * DOF]) const {
 #pragma unroll
         for (int c = 0; c < DOF; c++)

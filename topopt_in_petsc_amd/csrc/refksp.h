@@ -47,7 +47,9 @@ __global__ __launch_bounds__(BLK) void k_gs_wave(Op op, const double *__restrict
 #pragma unroll
         for (int c = 0; c < DOF; c++)
             if (backward ? c > r : c < r) ax = fma(D[r * DOF + c], xn[c] - xo[c], ax);
-        xn[r] = xo[r] + (b[n * DOF + r] - ax) / D[r * DOF + r];
+        // a Dirichlet row is the identity: its new value is b itself (xo + (b - xo) is b only to rounding unless xo is 0 or b,
+        // which is all PCSOR's zero guess ever gives it)
+        xn[r] = op.clamped(n, r) ? b[n * DOF + r] : xo[r] + (b[n * DOF + r] - ax) / D[r * DOF + r];
     }
 #pragma unroll
     for (int r = 0; r < DOF; r++) x[n * DOF + r] = xn[r];
@@ -166,17 +168,30 @@ struct RefKsp {
     }
 
     // ---- z = M^-1 r : PCJACOBI (pc = 0) or PCSOR (pc = 1) ---------------------------------------
+    // one in-place Gauss-Seidel sweep over the level, wavefront by wavefront (forward: t ascending, backward: descending)
     template <class Op>
-    int ssor(const Op &o, const double *r, double *z) {
+    int gs_sweep(const Op &o, const double *b, double *x, int backward) {
         const Geom &g = o.g;
         const int np = g.own_hi - g.own_lo + 1;
         const int T = (g.nx - 1) + 2 * (g.ny - 1) + 4 * (np - 1) + 1;
         const int nb = (int)(((long)g.ny * np + BLK - 1) / BLK);
-        for (int t = 0; t < T; t++) TP_LAUNCH((k_gs_wave<DOF, Op>), dim3(nb), dim3(BLK), 0, grid->stream, o, r, z, t, 0);
-        for (int t = T - 1; t >= 0; t--) TP_LAUNCH((k_gs_wave<DOF, Op>), dim3(nb), dim3(BLK), 0, grid->stream, o, r, z, t, 1);
-        grid->launches += 2 * T;
-        sweeps += 2;
+        for (int s = 0; s < T; s++)
+            TP_LAUNCH((k_gs_wave<DOF, Op>), dim3(nb), dim3(BLK), 0, grid->stream, o, b, x, backward ? T - 1 - s : s, backward);
+        grid->launches += T;
+        sweeps += 1;
         return TP_OK;
+    }
+    template <class Op>
+    int ssor(const Op &o, const double *r, double *z) {
+        TP_TRY(gs_sweep(o, r, z, 0));
+        return gs_sweep(o, r, z, 1);
+    }
+    // one sweep of level l on x in place, from the iterate x holds (tests: tp_elasticity_level_gs)
+    int gs(int l, int backward, const double *b, double *x) {
+        Level<DOF> &L = mg->lv[l];
+        if (L.kind == LV_MATFREE) return gs_sweep(MatfreeOp<DOF>{L.KE, L.E, L.mask, L.g}, b, x, backward);
+        if (L.kind == LV_DIA) return gs_sweep(DiaOp<DOF>{L.S, L.ndof(), L.g}, b, x, backward);
+        return TP_ERR_STATE;
     }
     int pc_apply(int l, int pc, const double *r, double *z) {
         Level<DOF> &L = mg->lv[l];

@@ -1311,6 +1311,15 @@ extern "C" int tp_elasticity_level_pc(tp_elasticity *e, int l, int pc, const dou
     TP_TRY(refksp_get(e->mg, &R));
     return R->pc_apply(l, pc, r, z);
 }
+// one in-place Gauss-Seidel sweep of level l on x from the iterate it holds (forward: backward == 0): PCSOR's own launches,
+// one half of them
+extern "C" int tp_elasticity_level_gs(tp_elasticity *e, int l, int backward, const double *b, double *x) {
+    if (!e || !e->assembled || l < 0 || l >= e->mg.nlv || e->mg.opt.ksp_mode != 1) return TP_ERR_STATE;
+    if (!b || !x) return TP_ERR_ARG;
+    RefKsp<3> *R;
+    TP_TRY(refksp_get(e->mg, &R));
+    return R->gs(l, backward != 0, b, x);
+}
 extern "C" int tp_elasticity_level_gmres(tp_elasticity *e, int l, int pc, int m, int its, double rtol, const double *b, double *x,
                                          int zero_guess, int *its_done) {
     if (!e->assembled || l < 0 || l >= e->mg.nlv || e->mg.opt.ksp_mode != 1) return TP_ERR_STATE;

@@ -141,6 +141,7 @@ SYMBOLS = {
     "tp_elasticity_set_cycles": (_i, [_vp, _vp, _i]),
     "tp_elasticity_precond": (_i, [_vp, _vp, _vp]),
     "tp_elasticity_level_pc": (_i, [_vp, _i, _i, _vp, _vp]),
+    "tp_elasticity_level_gs": (_i, [_vp, _i, _i, _vp, _vp]),
     "tp_elasticity_level_gmres": (_i, [_vp, _i, _i, _i, _i, _d, _vp, _vp, _i, C.POINTER(_i)]),
     "tp_elasticity_smooth": (_i, [_vp, _i, _vp, _vp, _i, _i]),
     "tp_elasticity_smooth_dot": (_i, [_vp, _i, _vp, _vp, _i, _i, C.POINTER(C.c_double)]),
