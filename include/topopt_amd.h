@@ -408,6 +408,22 @@ int tp_elasticity_petsc_options(const tp_elasticity *e, char *buf, size_t cap);
  * 2 = W; PETSc's form: same right-hand side, the next cycle starts from the previous one's iterate); one cycle into the
  * coarsest level whatever is set */
 int tp_elasticity_set_cycles(tp_elasticity *e, const int *cycles, int n);
+/* ---- the multigrid hierarchy level by level (tests, tools, bench.py) ----
+ * tp_elasticity_, tp_conduction_ and tp_pdefilter_ carry the same calls on their solver's levels (0 = the finest): level_count,
+ * level_nodes, level_lambda, level_lambda_min, level_apply, level_diag, smooth, level_residual, restrict, prolong_add,
+ * last_op_form, last_stats (the PDE filter: no level_residual, no last_stats).  Vectors: [dev, the level's local dofs].
+ * ONE contract, every rule answered before anything is launched or written, checked in this order:
+ *   1. a NULL handle, a NULL vector or output pointer (form4 too; the three of last_stats may be NULL), k < 0 in smooth:
+ *      TP_ERR_ARG.  level_count and level_nodes answer -TP_ERR_ARG, the lambdas NaN -- for a NULL handle or a level that is not
+ *      there; these four ask for no assembly.
+ *   2. a handle that cannot answer: elasticity and conduction TP_ERR_STATE before the first assemble (level_apply, level_diag,
+ *      smooth, level_residual, and the elasticity-only precond, level_pc, level_gs, level_gmres, smooth_dot); the PDE filter
+ *      TP_ERR_ARG on EVERY call for a filter that is not of type 2 (its hierarchy is complete from tp_filter_create on).
+ *      restrict, prolong_add, last_op_form and last_stats ask for no assembly.
+ *   3. a level the hierarchy does not have: TP_ERR_ARG; restrict and prolong_add go between level and level + 1 and need both.
+ * smooth with k == 0 is legal (the two copies alone), except on the PDE filter (TP_ERR_ARG).  What is particular to a call comes
+ * after these: TP_ERR_STATE from level_pc / level_gs / level_gmres outside ksp_mode 1 and from smooth_dot on a level whose kernel
+ * carries no fused dot. */
 int tp_elasticity_level_count(const tp_elasticity *e);
 long tp_elasticity_level_nodes(const tp_elasticity *e, int level);
 double tp_elasticity_level_lambda(const tp_elasticity *e, int level);
@@ -493,7 +509,8 @@ int tp_conduction_response(tp_conduction *c, int ncase,
         double *f_case, double *fx, double *gx, double *dfdx, double *dgdx);
 int tp_conduction_set_tolerances(tp_conduction *c, double rtol, double atol, double dtol, int max_it);   /* negative: keep */
 /* the hierarchy level by level, as the tp_elasticity_ calls of the same names; vectors [dev, the level's local nodes].
- * level_count / level_nodes answer -TP_ERR_ARG, the lambdas NaN, where the others answer TP_ERR_ARG. */
+ * level_count / level_nodes answer -TP_ERR_ARG, the lambdas NaN, where the others answer TP_ERR_ARG (the contract stated above
+ * tp_elasticity_level_count: this family's, now every family's). */
 int tp_conduction_level_count(const tp_conduction *c);
 long tp_conduction_level_nodes(const tp_conduction *c, int level);
 double tp_conduction_level_lambda(const tp_conduction *c, int level);
@@ -512,7 +529,9 @@ int tp_conduction_last_stats(const tp_conduction *c, double *alg_bytes, double *
 /* ---- density / sensitivity filter (Filter.cc) --------------------------- */
 typedef struct tp_filter tp_filter;
 /* Filter::Filter + SetUp (Filter.cc:25-38, :290-463).  filterType 0 = sensitivity,
- * 1 = density, 2 = PDE (Helmholtz), other = none; rmin is an absolute length. */
+ * 1 = density, 2 = PDE (Helmholtz), other = none; rmin is an absolute length.  Type 2: pde_opts (NULL: the reference's) are
+ * checked against the grid as tp_elasticity_create checks its own -- nlvls outside 1..TP_MAX_LEVELS, a mesh that does not coarsen
+ * nlvls - 1 times, a ksp_mode other than 0 or 1 (1: one device only) are TP_ERR_ARG -- without the slab-thickness rule. */
 int tp_filter_create(tp_filter **f, tp_grid *g, int filterType, double rmin, const tp_solver_opts *pde_opts);
 /* y = H x, the un-normalised cone filter: MatMult(H, x, y) of Filter.cc:68, :173, :181 (types 0, 1) */
 int tp_filter_mult_h(tp_filter *f, const double *x, double *y);
@@ -539,10 +558,10 @@ int tp_pdefilter_elem_to_node(tp_filter *f, const double *x_elem, double *rhs_no
 int tp_pdefilter_solve(tp_filter *f, const double *rhs_nodal, double *u_nodal);
 int tp_pdefilter_node_to_elem(tp_filter *f, const double *u_nodal, double *x_elem);
 int tp_pdefilter_apply(tp_filter *f, const double *u_nodal, double *y_nodal);
-/* The PDE filter's scalar multigrid hierarchy level by level, for tests: the counterparts of tp_elasticity_level_*,
- * _smooth, _restrict, _prolong_add and _last_op_form (level 0 of level_apply is tp_pdefilter_apply; level_diag exports
- * the reciprocal Jacobi diagonal).  Vectors: [dev, the level's local nodes].  A filter that is not of type 2, a level
- * it does not have or a null vector: TP_ERR_ARG (-TP_ERR_ARG from level_count / level_nodes, NaN from the lambdas). */
+/* The PDE filter's scalar multigrid hierarchy level by level, for tests: the contract stated above tp_elasticity_level_count
+ * (level 0 of level_apply is tp_pdefilter_apply; level_diag exports the reciprocal Jacobi diagonal).  Vectors: [dev, the level's
+ * local nodes].  Particular to the filter: anything but a filter of type 2 is TP_ERR_ARG on every call, smooth refuses k == 0,
+ * and there is no level_residual and no last_stats. */
 int tp_pdefilter_level_count(const tp_filter *f);
 long tp_pdefilter_level_nodes(const tp_filter *f, int level);
 double tp_pdefilter_level_lambda(const tp_filter *f, int level);

@@ -75,6 +75,110 @@ def _ptr(t):
     return t.data_ptr()
 
 
+class _Handle:
+    """A library object behind `handle`, made on a grid that adopted it (Grid._adopt): close() destroys it NOW -- Grid.close()
+    does that for every dependent before the grid goes -- and is idempotent; __del__ at the latest.  _destroy: the name of the
+    library's destroy call."""
+    _destroy = None
+
+    def close(self):
+        if getattr(self, "handle", None):
+            getattr(self.L, self._destroy)(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _Levels:
+    """The multigrid hierarchy of a handle level by level, for tests, tools and bench.py: the <_prefix>_level_* / _smooth /
+    _restrict / _prolong_add / _last_op_form calls of include/topopt_amd.h (one contract for the three families; csrc/mg_levels.h).
+    Vectors hold _dof values per local node of the level.  Every error answer raises TopOptError: a non-zero code, the negative
+    code of level_count / level_nodes, the NaN of the lambdas."""
+    _prefix, _dof = None, 1
+
+    def _level_fn(self, suffix):
+        name = "%s_%s" % (self._prefix, suffix)
+        return getattr(self.L, name), name
+
+    def _level_call(self, suffix, *args):
+        fn, name = self._level_fn(suffix)
+        _chk(fn(self.handle, *args), name)
+
+    def _level_value(self, suffix, *args):
+        """the four calls that answer a value: a count (-code: an error) or a lambda (NaN: TP_ERR_ARG)"""
+        fn, name = self._level_fn(suffix)
+        v = fn(self.handle, *args)
+        _chk((1 if v != v else 0) if isinstance(v, float) else max(-v, 0), name)
+        return v
+
+    def level_count(self):
+        return self._level_value("level_count")
+
+    def level_nodes(self, l):
+        return self._level_value("level_nodes", l)
+
+    def level_lambda(self, l):
+        return self._level_value("level_lambda", l)
+
+    def level_lambda_min(self, l):
+        return self._level_value("level_lambda_min", l)
+
+    def level_vec(self, l):
+        return torch.zeros(self._dof * self.level_nodes(l), dtype=torch.float64, device=self.grid.device)
+
+    def level_apply(self, l, u):
+        y = torch.zeros_like(u)
+        self._level_call("level_apply", l, _ptr(u), _ptr(y))
+        return y
+
+    def level_dinv(self, l):
+        d = self.level_vec(l)
+        self._level_call("level_diag", l, _ptr(d))
+        return d
+
+    def smooth(self, l, b, x, k, zero_guess=False):
+        self._level_call("smooth", l, _ptr(b), _ptr(x), k, int(zero_guess))
+        return x
+
+    def restrict(self, l, rf):
+        rc = self.level_vec(l + 1)
+        self._level_call("restrict", l, _ptr(rf), _ptr(rc))
+        return rc
+
+    def prolong_add(self, l, xc, xf):
+        self._level_call("prolong_add", l, _ptr(xc), _ptr(xf))
+        return xf
+
+    def last_op_form(self):
+        """(kind, a, b, c) of the last operator application (tp_elasticity_last_op_form): kind 1 fine tile kernel (generation,
+        tile 0 15x15 / 1 16x16 / 2 32x8, z-chunk), 2 level 1 from the fine densities (correction fused, -, z-chunk), 3 per-node
+        matrix-free, 4 stored stencil (threads per row, node form, mirrored reads).  Kind 3 on the scalar hierarchies: a = 2 the
+        register form of conduction.h, a = 1 the PDE filter's 27-point weight table, a = 0 the gather over the elements
+        (TP_NO_COND_STENCIL, TP_NO_PDE_STENCIL)"""
+        f = (C.c_int * 4)()
+        self._level_call("last_op_form", f)
+        return tuple(f)
+
+
+class _LevelStats(_Levels):
+    """... and the two calls that the elasticity and the conduction family have beside them"""
+
+    def level_residual(self, l, b, x):
+        """r = b - A_l x through the residual epilogue of the level's kernel, as the V-cycle forms it"""
+        r = torch.zeros_like(x)
+        self._level_call("level_residual", l, _ptr(b), _ptr(x), _ptr(r))
+        return r
+
+    def pop_stats(self):
+        b, f, n = C.c_double(), C.c_double(), C.c_long()
+        self._level_call("last_stats", C.byref(b), C.byref(f), C.byref(n))
+        return b.value, f.value, n.value
+
+
 @dataclass
 class SolverOptions:
     """LinearElasticity.cc:621-635 defaults; smoother = Chebyshev(nsmooth)/Jacobi."""
@@ -328,8 +432,9 @@ class Grid:
         _chk(self.L.tp_sync(self.handle), "tp_sync")
 
 
-class LinearElasticity:
+class LinearElasticity(_Handle, _LevelStats):
     """LinearElasticity (LinearElasticity.h:21-109) on the MI355X."""
+    _destroy, _prefix, _dof = "tp_elasticity_destroy", "tp_elasticity", 3
 
     def __init__(self, grid, opts=None):
         self.grid, self.L = grid, grid.L
@@ -359,17 +464,6 @@ class LinearElasticity:
         self._eig = None
         # buckling modes: the same for BucklingModes; the adjoint state of BucklingSensitivity persists too
         self._buck = self._buck_adj = self._buck_rhs = self._buck_row = None
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self.L.tp_elasticity_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     @property
     def KE(self):
@@ -1076,41 +1170,15 @@ class LinearElasticity:
             raise TopOptError(2, "tp_elasticity_petsc_options (no assembly yet)")
         return buf.value.decode()
 
-    def level_count(self):
-        return self.L.tp_elasticity_level_count(self.handle)
-
-    def level_nodes(self, l):
-        return self.L.tp_elasticity_level_nodes(self.handle, l)
-
-    def level_lambda(self, l):
-        return self.L.tp_elasticity_level_lambda(self.handle, l)
-
-    def level_lambda_min(self, l):
-        return self.L.tp_elasticity_level_lambda_min(self.handle, l)
-
     def coarse_direct_active(self):
         """rows of the coarsest level if the last assembly factored it (SolverOptions.coarse_direct), else 0"""
         return self.L.tp_elasticity_coarse_direct_active(self.handle)
 
     def xcd_status(self):
         """process-wide: (recoveries from one-XCD kernels that gave up, one-XCD forms off, factorisation no longer deferred)"""
-        import ctypes as C
         a, b, c = C.c_int(), C.c_int(), C.c_int()
         self.L.tp_xcd_status(C.byref(a), C.byref(b), C.byref(c))
         return a.value, bool(b.value), bool(c.value)
-
-    def level_vec(self, l):
-        return torch.zeros(3 * self.level_nodes(l), dtype=torch.float64, device=self.grid.device)
-
-    def level_apply(self, l, u):
-        y = torch.zeros_like(u)
-        _chk(self.L.tp_elasticity_level_apply(self.handle, l, _ptr(u), _ptr(y)), "tp_elasticity_level_apply")
-        return y
-
-    def level_dinv(self, l):
-        d = self.level_vec(l)
-        _chk(self.L.tp_elasticity_level_diag(self.handle, l, _ptr(d)), "tp_elasticity_level_diag")
-        return d
 
     def set_cycles(self, cycles):
         """PCMGSetCycleTypeOnLevel: cycles[l] cycles of level l + 1 per visit of level l (l = 0 finest; 1 = V, 2 = W)"""
@@ -1130,10 +1198,9 @@ class LinearElasticity:
 
     def level_gmres(self, l, pc, m, its, b, x, zero_guess=False, rtol=-1.0):
         """ksp_mode 1: the level's left-preconditioned GMRES(m), at most `its` iterations (rtol < 0: no test)"""
-        import ctypes
-        done = ctypes.c_int(0)
+        done = C.c_int(0)
         _chk(self.L.tp_elasticity_level_gmres(self.handle, l, pc, m, its, rtol, _ptr(b), _ptr(x), int(zero_guess),
-                                              ctypes.byref(done)), "tp_elasticity_level_gmres")
+                                              C.byref(done)), "tp_elasticity_level_gmres")
         return x, done.value
 
     def precond(self, r):
@@ -1141,43 +1208,11 @@ class LinearElasticity:
         _chk(self.L.tp_elasticity_precond(self.handle, _ptr(r), _ptr(z)), "tp_elasticity_precond")
         return z
 
-    def smooth(self, l, b, x, k, zero_guess=False):
-        _chk(self.L.tp_elasticity_smooth(self.handle, l, _ptr(b), _ptr(x), k, int(zero_guess)), "tp_elasticity_smooth")
-        return x
-
     def smooth_dot(self, l, b, x, k, zero_guess=False):
         """smooth() whose last step is the fused form that also returns b . x_out (CG's r . z): (x, dot)"""
         d = C.c_double()
         _chk(self.L.tp_elasticity_smooth_dot(self.handle, l, _ptr(b), _ptr(x), k, int(zero_guess), C.byref(d)), "tp_elasticity_smooth_dot")
         return x, d.value
-
-    def level_residual(self, l, b, x):
-        """r = b - A_l x through the residual epilogue of the level's kernel, as the V-cycle forms it"""
-        r = torch.zeros_like(x)
-        _chk(self.L.tp_elasticity_level_residual(self.handle, l, _ptr(b), _ptr(x), _ptr(r)), "tp_elasticity_level_residual")
-        return r
-
-    def restrict(self, l, rf):
-        rc = self.level_vec(l + 1)
-        _chk(self.L.tp_elasticity_restrict(self.handle, l, _ptr(rf), _ptr(rc)), "tp_elasticity_restrict")
-        return rc
-
-    def prolong_add(self, l, xc, xf):
-        _chk(self.L.tp_elasticity_prolong_add(self.handle, l, _ptr(xc), _ptr(xf)), "tp_elasticity_prolong_add")
-        return xf
-
-    def pop_stats(self):
-        b, f, n = C.c_double(), C.c_double(), C.c_long()
-        self.L.tp_elasticity_last_stats(self.handle, C.byref(b), C.byref(f), C.byref(n))
-        return b.value, f.value, n.value
-
-    def last_op_form(self):
-        """(kind, a, b, c) of the last operator application (tp_elasticity_last_op_form): kind 1 fine tile kernel (generation,
-        tile 0 15x15 / 1 16x16 / 2 32x8, z-chunk), 2 level 1 from the fine densities (correction fused, -, z-chunk), 3 per-node
-        matrix-free, 4 stored stencil (threads per row, node form, mirrored reads)"""
-        f = (C.c_int * 4)()
-        _chk(self.L.tp_elasticity_last_op_form(self.handle, f), "tp_elasticity_last_op_form")
-        return tuple(f)
 
 
 def heat_sink_and_load(nx, ny, nz, h, q0=1.0, node_z0=0, nz_local=None):
@@ -1197,9 +1232,10 @@ def heat_sink_and_load(nx, ny, nz, h, q0=1.0, node_z0=0, nz_local=None):
     return N.reshape(-1), (q0 * hx * hy * hz / 8.0 * cnt).reshape(-1)
 
 
-class HeatConduction:
+class HeatConduction(_Handle, _LevelStats):
     """Steady heat conduction on the MI355X (include/topopt_amd.h: tp_conduction): conductivity k = kmin + x^p (kmax - kmin) per
     element, temperature T per node, heat sink where N = 0.  Methods are named as on LinearElasticity."""
+    _destroy, _prefix, _dof = "tp_conduction_destroy", "tp_conduction", 1
 
     def __init__(self, grid, opts=None):
         self.grid, self.L = grid, grid.L
@@ -1212,17 +1248,6 @@ class HeatConduction:
         self.RHS = grid.node_vec(1)
         self.N = grid.node_vec(1)
         self.last_its, self.last_rnorm, self.last_bnorm, self.last_hist = 0, 0.0, 0.0, None
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self.L.tp_conduction_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     ncases = 1   # one load, one state: what the driver's records and restart files ask a physics object for
 
@@ -1320,65 +1345,10 @@ class HeatConduction:
         fx, gx, _ = self.Response([self.T], None, None, xPhys, kmin, kmax, penal, volfrac, dfdx, dgdx)
         return fx, gx
 
-    # ---- introspection used by the tests ----------------------------
-    def level_count(self):
-        return self.L.tp_conduction_level_count(self.handle)
 
-    def level_nodes(self, l):
-        return self.L.tp_conduction_level_nodes(self.handle, l)
-
-    def level_lambda(self, l):
-        return self.L.tp_conduction_level_lambda(self.handle, l)
-
-    def level_lambda_min(self, l):
-        return self.L.tp_conduction_level_lambda_min(self.handle, l)
-
-    def level_vec(self, l):
-        return torch.zeros(self.level_nodes(l), dtype=torch.float64, device=self.grid.device)
-
-    def level_apply(self, l, u):
-        y = torch.zeros_like(u)
-        _chk(self.L.tp_conduction_level_apply(self.handle, l, _ptr(u), _ptr(y)), "tp_conduction_level_apply")
-        return y
-
-    def level_dinv(self, l):
-        d = self.level_vec(l)
-        _chk(self.L.tp_conduction_level_diag(self.handle, l, _ptr(d)), "tp_conduction_level_diag")
-        return d
-
-    def smooth(self, l, b, x, k, zero_guess=False):
-        _chk(self.L.tp_conduction_smooth(self.handle, l, _ptr(b), _ptr(x), k, int(zero_guess)), "tp_conduction_smooth")
-        return x
-
-    def level_residual(self, l, b, x):
-        r = torch.zeros_like(x)
-        _chk(self.L.tp_conduction_level_residual(self.handle, l, _ptr(b), _ptr(x), _ptr(r)), "tp_conduction_level_residual")
-        return r
-
-    def restrict(self, l, rf):
-        rc = self.level_vec(l + 1)
-        _chk(self.L.tp_conduction_restrict(self.handle, l, _ptr(rf), _ptr(rc)), "tp_conduction_restrict")
-        return rc
-
-    def prolong_add(self, l, xc, xf):
-        _chk(self.L.tp_conduction_prolong_add(self.handle, l, _ptr(xc), _ptr(xf)), "tp_conduction_prolong_add")
-        return xf
-
-    def pop_stats(self):
-        b, f, n = C.c_double(), C.c_double(), C.c_long()
-        self.L.tp_conduction_last_stats(self.handle, C.byref(b), C.byref(f), C.byref(n))
-        return b.value, f.value, n.value
-
-    def last_op_form(self):
-        """(kind, a, b, c) of the last operator application: kind 3 per-node kernel (a = 2: the register form of conduction.h,
-        0: the gather over the elements), 4 stored stencil (threads per row, node form, mirrored reads)"""
-        f = (C.c_int * 4)()
-        _chk(self.L.tp_conduction_last_op_form(self.handle, f), "tp_conduction_last_op_form")
-        return tuple(f)
-
-
-class Filter:
+class Filter(_Handle, _Levels):
     """Filter (Filter.h:34-92): filterType 0 sensitivity, 1 density, 2 PDE."""
+    _destroy, _prefix, _dof = "tp_filter_destroy", "tp_pdefilter", 1
 
     def __init__(self, grid, filterType, rmin, pde_opts=None):
         self.grid, self.L = grid, grid.L
@@ -1388,17 +1358,6 @@ class Filter:
         _chk(self.L.tp_filter_create(C.byref(self.handle), grid.handle, filterType, rmin,
                                      C.byref(po) if po else None), "tp_filter_create")
         grid._adopt(self)
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self.L.tp_filter_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     @property
     def ElemConn(self):
@@ -1458,59 +1417,7 @@ class Filter:
         _chk(self.L.tp_pdefilter_node_to_elem(self.handle, _ptr(u), _ptr(x)), "tp_pdefilter_node_to_elem")
         return x
 
-    # ---- the PDE filter's scalar hierarchy level by level (tests): as LinearElasticity.level_* / smooth / restrict / ...
-    def level_count(self):
-        n = self.L.tp_pdefilter_level_count(self.handle)
-        _chk(-n if n < 0 else 0, "tp_pdefilter_level_count")
-        return n
-
-    def level_nodes(self, l):
-        n = self.L.tp_pdefilter_level_nodes(self.handle, l)
-        _chk(-n if n < 0 else 0, "tp_pdefilter_level_nodes")
-        return n
-
-    def level_lambda(self, l):
-        v = self.L.tp_pdefilter_level_lambda(self.handle, l)
-        _chk(1 if v != v else 0, "tp_pdefilter_level_lambda")
-        return v
-
-    def level_lambda_min(self, l):
-        v = self.L.tp_pdefilter_level_lambda_min(self.handle, l)
-        _chk(1 if v != v else 0, "tp_pdefilter_level_lambda_min")
-        return v
-
-    def level_vec(self, l):
-        return torch.zeros(self.level_nodes(l), dtype=torch.float64, device=self.grid.device)
-
-    def level_apply(self, l, u):
-        y = torch.zeros_like(u)
-        _chk(self.L.tp_pdefilter_level_apply(self.handle, l, _ptr(u), _ptr(y)), "tp_pdefilter_level_apply")
-        return y
-
-    def level_dinv(self, l):
-        d = self.level_vec(l)
-        _chk(self.L.tp_pdefilter_level_diag(self.handle, l, _ptr(d)), "tp_pdefilter_level_diag")
-        return d
-
-    def smooth(self, l, b, x, k, zero_guess=False):
-        _chk(self.L.tp_pdefilter_smooth(self.handle, l, _ptr(b), _ptr(x), k, int(zero_guess)), "tp_pdefilter_smooth")
-        return x
-
-    def restrict(self, l, rf):
-        rc = self.level_vec(l + 1)
-        _chk(self.L.tp_pdefilter_restrict(self.handle, l, _ptr(rf), _ptr(rc)), "tp_pdefilter_restrict")
-        return rc
-
-    def prolong_add(self, l, xc, xf):
-        _chk(self.L.tp_pdefilter_prolong_add(self.handle, l, _ptr(xc), _ptr(xf)), "tp_pdefilter_prolong_add")
-        return xf
-
-    def last_op_form(self):
-        """(kind, a, b, c) of the scalar hierarchy's last operator launch: (3, 1, 0, 0) the 27-point weight table, (3, 0, 0, 0)
-        the gather over the elements (TP_NO_PDE_STENCIL)"""
-        f = (C.c_int * 4)()
-        _chk(self.L.tp_pdefilter_last_op_form(self.handle, f), "tp_pdefilter_last_op_form")
-        return tuple(f)
+    # (type 2: the scalar hierarchy level by level is _Levels)
 
     def GetMND(self, x):
         v = C.c_double()
@@ -1523,26 +1430,16 @@ class Filter:
         return its.value, rn.value
 
 
-class LocalVolume:
+class LocalVolume(_Handle):
     """Local volume constraint (tp_localvol): the mean density in a ball of radius R around every element, its p-norm
     held below alpha as one constraint g = pn / alpha - 1.  Independent of the Filter and of rmin."""
+    _destroy = "tp_localvol_destroy"
 
     def __init__(self, grid, R):
         self.grid, self.L = grid, grid.L
         self.handle = C.c_void_p()
         _chk(self.L.tp_localvol_create(C.byref(self.handle), grid.handle, float(R)), "tp_localvol_create")
         grid._adopt(self)
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self.L.tp_localvol_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     @property
     def stencil_width(self):
@@ -1571,9 +1468,10 @@ class LocalVolume:
         return g.value, pn.value, mx.value
 
 
-class LengthScale:
+class LengthScale(_Handle):
     """Minimum length scale by geometric constraints (tp_lengthscale): one constraint for the solid and one for the void phase
     on the filtered field xTilde and the projected field xPhys, g = S / (n eps) - 1 with S = sum_e a_e exp(-c G_e) m_e^2."""
+    _destroy = "tp_lengthscale_destroy"
     KINDS = {"solid": 1, "void": 2, "both": 3}
 
     def __init__(self, grid):
@@ -1581,17 +1479,6 @@ class LengthScale:
         self.handle = C.c_void_p()
         _chk(self.L.tp_lengthscale_create(C.byref(self.handle), grid.handle), "tp_lengthscale_create")
         grid._adopt(self)
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self.L.tp_lengthscale_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def Constraints(self, xTilde, xPhys, c, eta_s=0.75, eta_v=0.25, eps=1e-2, kinds="both", projectionFilter=False, beta=0.1,
                     eta=0.0, dg_solid=None, dg_void=None):
@@ -1664,10 +1551,11 @@ def passive_labels(nxyz, xc, shapes):
     return lab.reshape(-1)
 
 
-class Passive:
+class Passive(_Handle):
     """Passive regions (tp_passive): labels per own element (0 active, 1 void, 2 solid) and the four kernels between the full
     fields the filter and the physics see and the packed vectors of the active elements the optimiser sees.  Every call takes a
     list of 1 to MAXVEC tensors and handles all of them in one launch."""
+    _destroy = "tp_passive_destroy"
     MAXVEC = _lib.PASSIVE_MAXVEC
 
     def __init__(self, grid, labels_own):
@@ -1680,17 +1568,6 @@ class Passive:
         _chk(self.L.tp_passive_create(C.byref(self.handle), grid.handle, lab.ctypes.data), "tp_passive_create")
         grid._adopt(self)
         self.n_active, self.n_void, self.n_solid = self.counts()
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self.L.tp_passive_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def counts(self):
         """(n_active, n_void, n_solid) of the own elements"""
@@ -1800,11 +1677,12 @@ def parse_link(spec, ne=None):
     return tuple(modes), tuple(cells)
 
 
-class Link:
+class Link(_Handle):
     """Design-variable linking (tp_link): per axis none, mirror, repeat:c or extrude, and the three maps between the
     reduced design the optimiser sees (the box nr_x x nr_y x nr_z, x fastest) and the full fields of the filter and the physics.
     Every call takes lists of 1 to MAXVEC tensors and handles all of them in one launch.  Fold's sum has one fixed order (ascending
     element order, the first member first), so its bits do not depend on the kernel form or the run."""
+    _destroy = "tp_link_destroy"
     MAXVEC = _lib.LINK_MAXVEC
 
     def __init__(self, grid, spec):
@@ -1816,17 +1694,6 @@ class Link:
              "tp_link_create")
         grid._adopt(self)
         self.n_reduced, self.nr = self.counts()
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self.L.tp_link_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def counts(self):
         """(own reduced variables, (nr_x, nr_y, nr_z))"""
@@ -1908,9 +1775,10 @@ class Robust:
         return rows
 
 
-class Overhang:
+class Overhang(_Handle):
     """Overhang (self-support) filter (tp_overhang): the printed density of a part built layer by layer along `build`
     ("+z", "-z", "+y", "-y"; the baseplate lies at the low end for +), and the transpose of its Jacobian."""
+    _destroy = "tp_overhang_destroy"
     BUILDS = {"+y": (1, 1), "-y": (1, -1), "+z": (2, 1), "-z": (2, -1)}
 
     def __init__(self, grid, build="+z"):
@@ -1920,17 +1788,6 @@ class Overhang:
         self.handle = C.c_void_p()
         _chk(self.L.tp_overhang_create(C.byref(self.handle), grid.handle, *self.BUILDS[build]), "tp_overhang_create")
         grid._adopt(self)
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self.L.tp_overhang_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def params(self, P=40.0, eps=1e-4, xi0=0.5):
         _chk(self.L.tp_overhang_set_params(self.handle, P, eps, xi0), "tp_overhang_set_params")
@@ -1957,11 +1814,12 @@ class Overhang:
         return a, w, p
 
 
-class Casting:
+class Casting(_Handle):
     """Casting (draw-direction) filter (tp_casting): the density of a part that leaves its mould along `draw` without an
     undercut or an enclosed cavity, and the transpose of its Jacobian.  `draw`: "+x", "-x", "+y", "-y", "+z", "-z" -- a
     one-sided mould, the part sitting on a base at the low end for + -- or "x:K", "y:K", "z:K", a two-sided mould whose plane
     parting surface lies between the element layers K - 1 and K (global)."""
+    _destroy = "tp_casting_destroy"
     AXES = {"x": 0, "y": 1, "z": 2}
 
     @classmethod
@@ -1985,17 +1843,6 @@ class Casting:
         self.handle = C.c_void_p()
         _chk(self.L.tp_casting_create(C.byref(self.handle), grid.handle, self.axis, self.parting), "tp_casting_create")
         grid._adopt(self)
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self.L.tp_casting_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def params(self, eps=1e-6):
         _chk(self.L.tp_casting_set_params(self.handle, eps), "tp_casting_set_params")
@@ -2022,8 +1869,9 @@ class Casting:
         return q
 
 
-class MMA:
+class MMA(_Handle):
     """MMA (MMA.h:29-140) on the device: the design vectors stay in HBM."""
+    _destroy = "tp_mma_destroy"
 
     def __init__(self, grid, x, m=1, n_global=None, a=None, c=None, d=None):
         """a, c, d: the subproblem's penalty numbers of the a/c/d constructors (MMA.cc:195-242), each a sequence of m
@@ -2046,17 +1894,6 @@ class MMA:
         if len(v) != self.m:
             raise ValueError("need %d values, got %d" % (self.m, len(v)))
         return (C.c_double * self.m)(*v)
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self.L.tp_mma_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def SetOuterMovelimit(self, Xmin, Xmax, movlim, x, xmin, xmax):
         _chk(self.L.tp_mma_set_outer_movelimit(self.handle, Xmin, Xmax, movlim, _ptr(x), _ptr(xmin), _ptr(xmax)),

@@ -25,18 +25,7 @@ static ConductionOp cond_op(const tp_conduction *c) {
 
 extern "C" int tp_conduction_create(tp_conduction **out, tp_grid *g, const tp_solver_opts *o) {
     if (!out || !g || !o) return TP_ERR_ARG;
-    if (o->nlvls < 1 || o->nlvls > TP_MAX_LEVELS) return TP_ERR_ARG;
-    const int f = 1 << (o->nlvls - 1);
-    if (g->ex % f || g->ey % f || g->ez_own % f) return TP_ERR_ARG;
-    if (o->ksp_mode != 0) return TP_ERR_ARG;   // (the reference's FGMRES configuration belongs to the elasticity solver)
-    if (g->has_comm) {  // as tp_elasticity_create: two element layers per rank on every level that stays distributed
-        const int last_distributed = o->nlvls >= 3 ? o->nlvls - 2 : o->nlvls - 1;
-        if ((g->ez_own >> last_distributed) < 2) {
-            fprintf(stderr, "topopt_amd: %d element layers per rank are too few for %d multigrid levels on slabs (need >= %d)\n",
-                    g->ez_own, o->nlvls, 2 << last_distributed);
-            return TP_ERR_ARG;
-        }
-    }
+    TP_TRY(check_solver_opts(g, o, false, true));   // (the reference's FGMRES configuration belongs to the elasticity solver)
     std::unique_ptr<tp_conduction> c(new tp_conduction());
     c->grid = g;
     c->resp_nb = 0;
@@ -257,79 +246,26 @@ extern "C" int tp_conduction_response(tp_conduction *c, int ncase, const double 
     return TP_OK;
 }
 
-// ---- level by level (tests): vectors [dev, the level's local nodes]
-static bool cond_level_ok(const tp_conduction *c, int l) { return l >= 0 && l < c->mg.nlv; }
-extern "C" int tp_conduction_level_count(const tp_conduction *c) { return c ? c->mg.nlv : -TP_ERR_ARG; }
-extern "C" long tp_conduction_level_nodes(const tp_conduction *c, int l) { return (c && cond_level_ok(c, l)) ? c->mg.lv[l].g.nodes() : -TP_ERR_ARG; }
-extern "C" double tp_conduction_level_lambda(const tp_conduction *c, int l) { return (c && cond_level_ok(c, l)) ? c->mg.lv[l].lam : NAN; }
-extern "C" double tp_conduction_level_lambda_min(const tp_conduction *c, int l) { return (c && cond_level_ok(c, l)) ? c->mg.lv[l].lam_min : NAN; }
-extern "C" int tp_conduction_level_apply(tp_conduction *c, int l, const double *u, double *y) {
-    if (!c || !u || !y) return TP_ERR_ARG;
-    if (!c->assembled) return TP_ERR_STATE;
-    if (!cond_level_ok(c, l)) return TP_ERR_ARG;
-    return c->mg.apply(l, const_cast<double *>(u), y);
+// ---- level by level (tests): vectors [dev, the level's local nodes]; mg_levels.h
+static LevelRef<1> levels(const tp_conduction *c) {
+    if (!c) return {nullptr, TP_ERR_ARG};
+    return {const_cast<MGSolver<1> *>(&c->mg), c->assembled ? TP_OK : TP_ERR_STATE};
 }
-extern "C" int tp_conduction_level_diag(tp_conduction *c, int l, double *d) {
-    if (!c || !d) return TP_ERR_ARG;
-    if (!c->assembled) return TP_ERR_STATE;
-    if (!cond_level_ok(c, l)) return TP_ERR_ARG;
-    Level<1> &L = c->mg.lv[l];
-    TP_HIP(hipMemcpyAsync(d, L.dinv, sizeof(double) * (size_t)L.ndof(), hipMemcpyDeviceToDevice, c->grid->stream));
-    return TP_OK;
-}
+extern "C" int tp_conduction_level_count(const tp_conduction *c) { return lv_count(levels(c)); }
+extern "C" long tp_conduction_level_nodes(const tp_conduction *c, int l) { return lv_nodes(levels(c), l); }
+extern "C" double tp_conduction_level_lambda(const tp_conduction *c, int l) { return lv_lambda(levels(c), l); }
+extern "C" double tp_conduction_level_lambda_min(const tp_conduction *c, int l) { return lv_lambda_min(levels(c), l); }
+extern "C" int tp_conduction_level_apply(tp_conduction *c, int l, const double *u, double *y) { return lv_apply(levels(c), l, u, y); }
+extern "C" int tp_conduction_level_diag(tp_conduction *c, int l, double *d) { return lv_diag(levels(c), l, d); }
 extern "C" int tp_conduction_smooth(tp_conduction *c, int l, const double *b, double *x, int k, int zero_guess) {
-    if (!c || !b || !x || k < 0) return TP_ERR_ARG;
-    if (!c->assembled) return TP_ERR_STATE;
-    if (!cond_level_ok(c, l)) return TP_ERR_ARG;
-    MGSolver<1> &mg = c->mg;
-    Level<1> &L = mg.lv[l];
-    const size_t nb = sizeof(double) * (size_t)L.ndof();
-    if (!zero_guess) TP_HIP(hipMemcpyAsync(L.x, x, nb, hipMemcpyDeviceToDevice, c->grid->stream));
-    TP_TRY(mg.smooth(l, b, k, zero_guess != 0));
-    TP_TRY(mg.drain_halos());
-    TP_HIP(hipMemcpyAsync(x, L.x, nb, hipMemcpyDeviceToDevice, c->grid->stream));
-    return TP_OK;
+    return lv_smooth(levels(c), l, b, x, k, zero_guess);
 }
 extern "C" int tp_conduction_level_residual(tp_conduction *c, int l, const double *b, const double *x, double *r) {
-    if (!c || !b || !x || !r) return TP_ERR_ARG;
-    if (!c->assembled) return TP_ERR_STATE;
-    if (!cond_level_ok(c, l)) return TP_ERR_ARG;
-    MGSolver<1> &mg = c->mg;
-    TP_TRY(mg.halo(l, const_cast<double *>(x)));
-    NodeArgs a{};
-    a.x = x;
-    a.out = r;
-    a.b = b;
-    TP_TRY(mg.op<EPI_RESID>(l, a));
-    return mg.drain_halos();
+    return lv_residual(levels(c), l, b, x, r);
 }
-extern "C" int tp_conduction_restrict(tp_conduction *c, int l, const double *rf, double *rc) {
-    if (!c || !rf || !rc || l < 0 || l + 1 >= c->mg.nlv) return TP_ERR_ARG;
-    MGSolver<1> &mg = c->mg;
-    TP_TRY(mg.halo(l, const_cast<double *>(rf)));
-    const Geom &C = mg.lv[l + 1].g;
-    TP_LAUNCH((k_restrict<1>), dim3((int)((C.owned_nodes() + BLK - 1) / BLK)), dim3(BLK), 0, c->grid->stream, C, mg.lv[l].g, rf, rc);
-    return TP_OK;
-}
-extern "C" int tp_conduction_prolong_add(tp_conduction *c, int l, const double *xc, double *xf) {
-    if (!c || !xc || !xf || l < 0 || l + 1 >= c->mg.nlv) return TP_ERR_ARG;
-    MGSolver<1> &mg = c->mg;
-    TP_TRY(mg.halo(l + 1, const_cast<double *>(xc)));
-    TP_LAUNCH((k_prolong_add<1>), dim3((int)((mg.lv[l].g.owned_nodes() + BLK - 1) / BLK)), dim3(BLK), 0, c->grid->stream, mg.lv[l + 1].g,
-              mg.lv[l].g, xc, xf);
-    return TP_OK;
-}
-extern "C" int tp_conduction_last_op_form(const tp_conduction *c, int *form4) {
-    if (!c || !form4) return TP_ERR_ARG;
-    for (int i = 0; i < 4; i++) form4[i] = c->mg.last_form[i];
-    return TP_OK;
-}
+extern "C" int tp_conduction_restrict(tp_conduction *c, int l, const double *rf, double *rc) { return lv_restrict(levels(c), l, rf, rc); }
+extern "C" int tp_conduction_prolong_add(tp_conduction *c, int l, const double *xc, double *xf) { return lv_prolong_add(levels(c), l, xc, xf); }
+extern "C" int tp_conduction_last_op_form(const tp_conduction *c, int *form4) { return lv_last_op_form(levels(c), form4); }
 extern "C" int tp_conduction_last_stats(const tp_conduction *c, double *alg_bytes, double *flops, long *launches) {
-    if (!c || !c->grid) return TP_ERR_ARG;
-    if (alg_bytes) *alg_bytes = c->grid->alg_bytes;
-    if (flops) *flops = c->grid->flops;
-    if (launches) *launches = c->grid->launches;
-    c->grid->alg_bytes = c->grid->flops = 0.0;
-    c->grid->launches = 0;
-    return TP_OK;
+    return lv_last_stats(levels(c), alg_bytes, flops, launches);
 }

@@ -545,55 +545,21 @@ extern "C" int tp_pdefilter_apply(tp_filter *f, const double *u_nodal, double *y
     return f->pde->apply(0, const_cast<double *>(u_nodal), y_nodal);
 }
 
-// ---- the scalar hierarchy level by level, for tests (the counterparts of tp_elasticity_level_* / _smooth / _restrict /
-// _prolong_add / _last_op_form).  Anything but a PDE filter and a level of its own: an error, nothing is dereferenced.
-static inline bool pde_level_ok(const tp_filter *f, int l) { return f && f->type == 2 && f->pde && l >= 0 && l < f->pde->nlv; }
-extern "C" int tp_pdefilter_level_count(const tp_filter *f) { return pde_level_ok(f, 0) ? f->pde->nlv : -TP_ERR_ARG; }
-extern "C" long tp_pdefilter_level_nodes(const tp_filter *f, int l) { return pde_level_ok(f, l) ? f->pde->lv[l].g.nodes() : -(long)TP_ERR_ARG; }
-extern "C" double tp_pdefilter_level_lambda(const tp_filter *f, int l) { return pde_level_ok(f, l) ? f->pde->lv[l].lam : NAN; }
-extern "C" double tp_pdefilter_level_lambda_min(const tp_filter *f, int l) { return pde_level_ok(f, l) ? f->pde->lv[l].lam_min : NAN; }
-extern "C" int tp_pdefilter_level_apply(tp_filter *f, int l, const double *u, double *y) {
-    if (!pde_level_ok(f, l) || !u || !y) return TP_ERR_ARG;
-    return f->pde->apply(l, const_cast<double *>(u), y);
-}
-extern "C" int tp_pdefilter_level_diag(tp_filter *f, int l, double *d) {
-    if (!pde_level_ok(f, l) || !d) return TP_ERR_ARG;
-    Level<1> &L = f->pde->lv[l];
-    TP_HIP(hipMemcpyAsync(d, L.dinv, sizeof(double) * (size_t)L.ndof(), hipMemcpyDeviceToDevice, f->grid->stream));
-    return TP_OK;
-}
+// ---- the scalar hierarchy level by level, for tests (mg_levels.h).  Anything but a PDE filter: TP_ERR_ARG on every call,
+// nothing is dereferenced; the hierarchy is complete from creation on, so no call waits for an assembly.
+static LevelRef<1> levels(const tp_filter *f) { return {f && f->type == 2 ? f->pde.get() : nullptr, TP_OK}; }
+extern "C" int tp_pdefilter_level_count(const tp_filter *f) { return lv_count(levels(f)); }
+extern "C" long tp_pdefilter_level_nodes(const tp_filter *f, int l) { return lv_nodes(levels(f), l); }
+extern "C" double tp_pdefilter_level_lambda(const tp_filter *f, int l) { return lv_lambda(levels(f), l); }
+extern "C" double tp_pdefilter_level_lambda_min(const tp_filter *f, int l) { return lv_lambda_min(levels(f), l); }
+extern "C" int tp_pdefilter_level_apply(tp_filter *f, int l, const double *u, double *y) { return lv_apply(levels(f), l, u, y); }
+extern "C" int tp_pdefilter_level_diag(tp_filter *f, int l, double *d) { return lv_diag(levels(f), l, d); }
 extern "C" int tp_pdefilter_smooth(tp_filter *f, int l, const double *b, double *x, int k, int zero_guess) {
-    if (!pde_level_ok(f, l) || !b || !x || k < 1) return TP_ERR_ARG;
-    MGSolver<1> &mg = *f->pde;
-    Level<1> &L = mg.lv[l];
-    const size_t nb = sizeof(double) * (size_t)L.ndof();
-    if (!zero_guess) TP_HIP(hipMemcpyAsync(L.x, x, nb, hipMemcpyDeviceToDevice, f->grid->stream));
-    TP_TRY(mg.smooth(l, b, k, zero_guess != 0));
-    TP_TRY(mg.drain_halos());
-    TP_HIP(hipMemcpyAsync(x, L.x, nb, hipMemcpyDeviceToDevice, f->grid->stream));
-    return TP_OK;
+    return k == 0 ? TP_ERR_ARG : lv_smooth(levels(f), l, b, x, k, zero_guess);   // (no copies-only call here)
 }
-extern "C" int tp_pdefilter_restrict(tp_filter *f, int l, const double *rf, double *rc) {
-    if (!pde_level_ok(f, l) || !pde_level_ok(f, l + 1) || !rf || !rc) return TP_ERR_ARG;
-    MGSolver<1> &mg = *f->pde;
-    TP_TRY(mg.halo(l, const_cast<double *>(rf)));
-    const Geom &C = mg.lv[l + 1].g;
-    TP_LAUNCH((k_restrict<1>), dim3((int)((C.owned_nodes() + BLK - 1) / BLK)), dim3(BLK), 0, f->grid->stream, C, mg.lv[l].g, rf, rc);
-    return TP_OK;
-}
-extern "C" int tp_pdefilter_prolong_add(tp_filter *f, int l, const double *xc, double *xf) {
-    if (!pde_level_ok(f, l) || !pde_level_ok(f, l + 1) || !xc || !xf) return TP_ERR_ARG;
-    MGSolver<1> &mg = *f->pde;
-    TP_TRY(mg.halo(l + 1, const_cast<double *>(xc)));
-    TP_LAUNCH((k_prolong_add<1>), dim3((int)((mg.lv[l].g.owned_nodes() + BLK - 1) / BLK)), dim3(BLK), 0, f->grid->stream, mg.lv[l + 1].g,
-              mg.lv[l].g, xc, xf);
-    return TP_OK;
-}
-extern "C" int tp_pdefilter_last_op_form(const tp_filter *f, int *form4) {
-    if (!pde_level_ok(f, 0) || !form4) return TP_ERR_ARG;
-    for (int i = 0; i < 4; i++) form4[i] = f->pde->last_form[i];
-    return TP_OK;
-}
+extern "C" int tp_pdefilter_restrict(tp_filter *f, int l, const double *rf, double *rc) { return lv_restrict(levels(f), l, rf, rc); }
+extern "C" int tp_pdefilter_prolong_add(tp_filter *f, int l, const double *xc, double *xf) { return lv_prolong_add(levels(f), l, xc, xf); }
+extern "C" int tp_pdefilter_last_op_form(const tp_filter *f, int *form4) { return lv_last_op_form(levels(f), form4); }
 
 // y = H x, the un-normalised cone filter (MatMult(H, x, y) of Filter.cc:68, :173, :181); types 0 and 1
 extern "C" int tp_filter_mult_h(tp_filter *f, const double *x, double *y) {
@@ -651,13 +617,7 @@ extern "C" int tp_filter_create(tp_filter **out, tp_grid *g, int filterType, dou
             o.nsmooth = 2;
             o.ncoarse = 10;    // :357
         }
-        const int fdiv = 1 << (o.nlvls - 1);
-        if (g->ex % fdiv || g->ey % fdiv || g->ez_own % fdiv) return TP_ERR_ARG;
-        if (o.ksp_mode != 0 && o.ksp_mode != 1) return TP_ERR_ARG;
-        if (o.ksp_mode == 1 && g->has_comm) {
-            fprintf(stderr, "topopt_amd: ksp_mode 1 (the reference's FGMRES / GMRES configuration) runs on one device only\n");
-            return TP_ERR_ARG;
-        }
+        TP_TRY(check_solver_opts(g, &o, true, false));
         f->elemVol = dx * dy * dz;
         f->KF.resize((size_t)64 * o.nlvls);
         helmholtz_element_box(dx, dy, dz, rmin / 2.0 / sqrt(3), f->KF.data());  // R conversion, :30

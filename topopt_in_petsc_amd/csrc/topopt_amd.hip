@@ -5,6 +5,7 @@
 
 #include "elements.h"
 #include "mg.h"
+#include "mg_levels.h"
 #include "refksp.h"
 #include "rccl_comm.h"
 
@@ -547,6 +548,11 @@ struct tp_elasticity {
     }
 };
 
+static LevelRef<3> levels(const tp_elasticity *e) {
+    if (!e) return {nullptr, TP_ERR_ARG};
+    return {const_cast<MGSolver<3> *>(&e->mg), e->assembled ? TP_OK : TP_ERR_STATE};
+}
+
 __global__ __launch_bounds__(BLK) void k_simp(const double *__restrict__ x, double Emin, double Emax, double penal,
                                               double *__restrict__ E, long n) {
     for (long i = blockIdx.x * (long)BLK + threadIdx.x; i < n; i += (long)gridDim.x * BLK)
@@ -583,26 +589,7 @@ extern "C" int tp_elasticity_create(tp_elasticity **out, tp_grid *g, const tp_so
 // MatSetValuesLocal hands over the matrix it computed itself, LinearElasticity.cc:118-123, :519-524)
 extern "C" int tp_elasticity_create_ke(tp_elasticity **out, tp_grid *g, const tp_solver_opts *o, const double *ke_host_576) {
     if (!out || !g || !o) return TP_ERR_ARG;
-    if (o->nlvls < 1 || o->nlvls > TP_MAX_LEVELS) return TP_ERR_ARG;
-    // TopOpt.cc:183-201: every direction divisible by 2^(nlvls-1); here also per slab
-    const int f = 1 << (o->nlvls - 1);
-    if (g->ex % f || g->ey % f || g->ez_own % f) return TP_ERR_ARG;
-    if (o->ksp_mode != 0 && o->ksp_mode != 1) return TP_ERR_ARG;
-    if (o->ksp_mode == 1 && g->has_comm) {
-        fprintf(stderr, "topopt_amd: ksp_mode 1 (the reference's FGMRES / GMRES / SOR configuration) runs on one device only\n");
-        return TP_ERR_ARG;
-    }
-    // slabs: every level that stays distributed keeps at least two element layers per rank (the boundary-first halo
-    // overlap and the level-1 ghost rows assume a rank's two boundary planes are distinct); the replicated coarsest
-    // level (three or more levels) may come down to one.  Decided from global sizes: the same answer on every rank.
-    if (g->has_comm) {
-        const int last_distributed = o->nlvls >= 3 ? o->nlvls - 2 : o->nlvls - 1;
-        if ((g->ez_own >> last_distributed) < 2) {
-            fprintf(stderr, "topopt_amd: %d element layers per rank are too few for %d multigrid levels on slabs (need >= %d)\n",
-                    g->ez_own, o->nlvls, 2 << last_distributed);
-            return TP_ERR_ARG;
-        }
-    }
+    TP_TRY(check_solver_opts(g, o, true, true));
     std::unique_ptr<tp_elasticity> e(new tp_elasticity());
     e->grid = g;
     e->mg.grid = g;
@@ -1288,25 +1275,20 @@ extern "C" int tp_elasticity_set_cycles(tp_elasticity *e, const int *cycles, int
     }
     return TP_OK;
 }
-extern "C" int tp_elasticity_level_count(const tp_elasticity *e) { return e->mg.nlv; }
-extern "C" long tp_elasticity_level_nodes(const tp_elasticity *e, int l) { return e->mg.lv[l].g.nodes(); }
-extern "C" double tp_elasticity_level_lambda(const tp_elasticity *e, int l) { return e->mg.lv[l].lam; }
-extern "C" double tp_elasticity_level_lambda_min(const tp_elasticity *e, int l) { return e->mg.lv[l].lam_min; }
-extern "C" int tp_elasticity_coarse_direct_active(const tp_elasticity *e) { return e->assembled && e->mg.cd.factored ? e->mg.cd.g.n : 0; }
-extern "C" int tp_elasticity_level_apply(tp_elasticity *e, int l, const double *u, double *y) {
-    if (!e->assembled || l < 0 || l >= e->mg.nlv) return TP_ERR_STATE;
-    return e->mg.apply(l, const_cast<double *>(u), y);
+extern "C" int tp_elasticity_level_count(const tp_elasticity *e) { return lv_count(levels(e)); }
+extern "C" long tp_elasticity_level_nodes(const tp_elasticity *e, int l) { return lv_nodes(levels(e), l); }
+extern "C" double tp_elasticity_level_lambda(const tp_elasticity *e, int l) { return lv_lambda(levels(e), l); }
+extern "C" double tp_elasticity_level_lambda_min(const tp_elasticity *e, int l) { return lv_lambda_min(levels(e), l); }
+extern "C" int tp_elasticity_coarse_direct_active(const tp_elasticity *e) {
+    return lv_guard(levels(e), true, 0) == TP_OK && e->mg.cd.factored ? e->mg.cd.g.n : 0;
 }
-extern "C" int tp_elasticity_level_diag(tp_elasticity *e, int l, double *d) {
-    if (!e->assembled) return TP_ERR_STATE;
-    Level<3> &L = e->mg.lv[l];
-    TP_HIP(hipMemcpyAsync(d, L.dinv, sizeof(double) * (size_t)L.ndof(), hipMemcpyDeviceToDevice, e->grid->stream));
-    return TP_OK;
-}
+extern "C" int tp_elasticity_level_apply(tp_elasticity *e, int l, const double *u, double *y) { return lv_apply(levels(e), l, u, y); }
+extern "C" int tp_elasticity_level_diag(tp_elasticity *e, int l, double *d) { return lv_diag(levels(e), l, d); }
 // ksp_mode 1 building blocks, level by level (tests): z = M^-1 r with PCJACOBI (pc 0) / PCSOR (pc 1), and the level's
 // GMRES(m) run for its iterations on x (zero_guess: x is zeroed first; rtol < 0: no convergence test)
 extern "C" int tp_elasticity_level_pc(tp_elasticity *e, int l, int pc, const double *r, double *z) {
-    if (!e->assembled || l < 0 || l >= e->mg.nlv || e->mg.opt.ksp_mode != 1) return TP_ERR_STATE;
+    TP_TRY(lv_guard(levels(e), r && z, l));
+    if (e->mg.opt.ksp_mode != 1) return TP_ERR_STATE;
     RefKsp<3> *R;
     TP_TRY(refksp_get(e->mg, &R));
     return R->pc_apply(l, pc, r, z);
@@ -1314,21 +1296,22 @@ extern "C" int tp_elasticity_level_pc(tp_elasticity *e, int l, int pc, const dou
 // one in-place Gauss-Seidel sweep of level l on x from the iterate it holds (forward: backward == 0): PCSOR's own launches,
 // one half of them
 extern "C" int tp_elasticity_level_gs(tp_elasticity *e, int l, int backward, const double *b, double *x) {
-    if (!e || !e->assembled || l < 0 || l >= e->mg.nlv || e->mg.opt.ksp_mode != 1) return TP_ERR_STATE;
-    if (!b || !x) return TP_ERR_ARG;
+    TP_TRY(lv_guard(levels(e), b && x, l));
+    if (e->mg.opt.ksp_mode != 1) return TP_ERR_STATE;
     RefKsp<3> *R;
     TP_TRY(refksp_get(e->mg, &R));
     return R->gs(l, backward != 0, b, x);
 }
 extern "C" int tp_elasticity_level_gmres(tp_elasticity *e, int l, int pc, int m, int its, double rtol, const double *b, double *x,
                                          int zero_guess, int *its_done) {
-    if (!e->assembled || l < 0 || l >= e->mg.nlv || e->mg.opt.ksp_mode != 1) return TP_ERR_STATE;
+    TP_TRY(lv_guard(levels(e), b && x, l));
+    if (e->mg.opt.ksp_mode != 1) return TP_ERR_STATE;
     RefKsp<3> *R;
     TP_TRY(refksp_get(e->mg, &R));
     return R->gmres(l, b, x, zero_guess != 0, m, its, rtol < 0 ? 0.0 : rtol, e->mg.opt.atol, e->mg.opt.dtol, rtol >= 0, pc, its_done);
 }
 extern "C" int tp_elasticity_precond(tp_elasticity *e, const double *r, double *z) {
-    if (!e->assembled) return TP_ERR_STATE;
+    TP_TRY(lv_guard(levels(e), r && z, 0));
     double *zp;
     TP_TRY(e->mg.precond(r, &zp));
     TP_HIP(hipMemcpyAsync(z, zp, sizeof(double) * (size_t)e->mg.lv[0].ndof(), hipMemcpyDeviceToDevice,
@@ -1336,20 +1319,12 @@ extern "C" int tp_elasticity_precond(tp_elasticity *e, const double *r, double *
     return TP_OK;
 }
 extern "C" int tp_elasticity_smooth(tp_elasticity *e, int l, const double *b, double *x, int k, int zero_guess) {
-    if (!e->assembled || l < 0 || l >= e->mg.nlv) return TP_ERR_STATE;
-    Level<3> &L = e->mg.lv[l];
-    const size_t nb = sizeof(double) * (size_t)L.ndof();
-    if (!zero_guess) TP_HIP(hipMemcpyAsync(L.x, x, nb, hipMemcpyDeviceToDevice, e->grid->stream));
-    TP_TRY(e->mg.smooth(l, b, k, zero_guess != 0));
-    TP_TRY(e->mg.drain_halos());
-    TP_HIP(hipMemcpyAsync(x, L.x, nb, hipMemcpyDeviceToDevice, e->grid->stream));
-    return TP_OK;
+    return lv_smooth(levels(e), l, b, x, k, zero_guess);
 }
 // smooth() with a dot slot: the last step is the fused EPI_CHEB_DOT and *dot = b . x_out (all ranks).  TP_ERR_STATE where the
 // level's kernel carries no fused dot; TP_ERR_ARG where no operator step would run (k < 1, or the zero guess with k < 2).
 extern "C" int tp_elasticity_smooth_dot(tp_elasticity *e, int l, const double *b, double *x, int k, int zero_guess, double *dot) {
-    if (!e || !e->assembled || l < 0 || l >= e->mg.nlv) return TP_ERR_STATE;
-    if (!b || !x || !dot || k < (zero_guess ? 2 : 1)) return TP_ERR_ARG;
+    TP_TRY(lv_guard(levels(e), b && x && dot && k >= (zero_guess ? 2 : 1), l));
     MGSolver<3> &mg = e->mg;
     if (mg.fine_generation(mg.lv[l]) < 2) return TP_ERR_STATE;  // as op<EPI_CHEB_DOT> would say, before anything is launched
     Level<3> &L = mg.lv[l];
@@ -1361,49 +1336,15 @@ extern "C" int tp_elasticity_smooth_dot(tp_elasticity *e, int l, const double *b
     TP_HIP(hipMemcpyAsync(x, L.x, nb, hipMemcpyDeviceToDevice, e->grid->stream));
     return read_scal(e->grid, S_TMP, 1, dot);
 }
-// r = b - A_l x through the residual epilogue of the level's kernel, as the V-cycle forms it (ghost planes of x refreshed first)
 extern "C" int tp_elasticity_level_residual(tp_elasticity *e, int l, const double *b, const double *x, double *r) {
-    if (!e || !e->assembled || l < 0 || l >= e->mg.nlv) return TP_ERR_STATE;
-    if (!b || !x || !r) return TP_ERR_ARG;
-    MGSolver<3> &mg = e->mg;
-    TP_TRY(mg.halo(l, const_cast<double *>(x)));
-    NodeArgs a{};
-    a.x = x;
-    a.out = r;
-    a.b = b;
-    TP_TRY(mg.op<EPI_RESID>(l, a));
-    return mg.drain_halos();
+    return lv_residual(levels(e), l, b, x, r);
 }
-extern "C" int tp_elasticity_restrict(tp_elasticity *e, int l, const double *rf, double *rc) {
-    MGSolver<3> &mg = e->mg;
-    if (l < 0 || l + 1 >= mg.nlv) return TP_ERR_ARG;
-    TP_TRY(mg.halo(l, const_cast<double *>(rf)));
-    const Geom &C = mg.lv[l + 1].g;
-    TP_LAUNCH((k_restrict<3>), dim3((int)((C.owned_nodes() + BLK - 1) / BLK)), dim3(BLK), 0,
-                       e->grid->stream, C, mg.lv[l].g, rf, rc);
-    return TP_OK;
-}
-extern "C" int tp_elasticity_prolong_add(tp_elasticity *e, int l, const double *xc, double *xf) {
-    MGSolver<3> &mg = e->mg;
-    if (l < 0 || l + 1 >= mg.nlv) return TP_ERR_ARG;
-    TP_TRY(mg.halo(l + 1, const_cast<double *>(xc)));
-    TP_LAUNCH((k_prolong_add<3>), dim3((int)((mg.lv[l].g.owned_nodes() + BLK - 1) / BLK)), dim3(BLK), 0,
-                       e->grid->stream, mg.lv[l + 1].g, mg.lv[l].g, xc, xf);
-    return TP_OK;
-}
+extern "C" int tp_elasticity_restrict(tp_elasticity *e, int l, const double *rf, double *rc) { return lv_restrict(levels(e), l, rf, rc); }
+extern "C" int tp_elasticity_prolong_add(tp_elasticity *e, int l, const double *xc, double *xf) { return lv_prolong_add(levels(e), l, xc, xf); }
 extern "C" int tp_elasticity_last_stats(const tp_elasticity *e, double *alg_bytes, double *flops, long *launches) {
-    if (alg_bytes) *alg_bytes = e->grid->alg_bytes;
-    if (flops) *flops = e->grid->flops;
-    if (launches) *launches = e->grid->launches;
-    e->grid->alg_bytes = e->grid->flops = 0.0;
-    e->grid->launches = 0;
-    return TP_OK;
+    return lv_last_stats(levels(e), alg_bytes, flops, launches);
 }
-extern "C" int tp_elasticity_last_op_form(const tp_elasticity *e, int *form4) {
-    if (!e || !form4) return TP_ERR_ARG;
-    for (int i = 0; i < 4; i++) form4[i] = e->mg.last_form[i];
-    return TP_OK;
-}
+extern "C" int tp_elasticity_last_op_form(const tp_elasticity *e, int *form4) { return lv_last_op_form(levels(e), form4); }
 
 // ===========================================================================
 // responses of the state: compliance of one or several load cases, von Mises stress p-norm, self-weight, thermal expansion, the mass operator and

@@ -130,26 +130,14 @@ SYMBOLS = {
     "tp_elasticity_geom_adjoint_rhs": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_d), _vp, _d, _d, _d, _vp]),
     "tp_elasticity_get_geom_tables": (_i, [_vp, _vp, _vp]),
     "tp_elasticity_petsc_options": (_i, [_vp, C.c_char_p, C.c_size_t]),
-    "tp_elasticity_level_count": (_i, [_vp]),
-    "tp_elasticity_level_nodes": (_l, [_vp, _i]),
-    "tp_elasticity_level_lambda": (_d, [_vp, _i]),
-    "tp_elasticity_level_lambda_min": (_d, [_vp, _i]),
     "tp_elasticity_coarse_direct_active": (_i, [_vp]),
     "tp_xcd_status": (_i, [C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
-    "tp_elasticity_level_apply": (_i, [_vp, _i, _vp, _vp]),
-    "tp_elasticity_level_diag": (_i, [_vp, _i, _vp]),
     "tp_elasticity_set_cycles": (_i, [_vp, _vp, _i]),
     "tp_elasticity_precond": (_i, [_vp, _vp, _vp]),
     "tp_elasticity_level_pc": (_i, [_vp, _i, _i, _vp, _vp]),
     "tp_elasticity_level_gs": (_i, [_vp, _i, _i, _vp, _vp]),
     "tp_elasticity_level_gmres": (_i, [_vp, _i, _i, _i, _i, _d, _vp, _vp, _i, C.POINTER(_i)]),
-    "tp_elasticity_smooth": (_i, [_vp, _i, _vp, _vp, _i, _i]),
     "tp_elasticity_smooth_dot": (_i, [_vp, _i, _vp, _vp, _i, _i, C.POINTER(C.c_double)]),
-    "tp_elasticity_level_residual": (_i, [_vp, _i, _vp, _vp, _vp]),
-    "tp_elasticity_restrict": (_i, [_vp, _i, _vp, _vp]),
-    "tp_elasticity_prolong_add": (_i, [_vp, _i, _vp, _vp]),
-    "tp_elasticity_last_stats": (_i, [_vp, C.POINTER(_d), C.POINTER(_d), C.POINTER(_l)]),
-    "tp_elasticity_last_op_form": (_i, [_vp, C.POINTER(_i)]),
     "tp_filter_create": (_i, [C.POINTER(_vp), _vp, _i, _d, C.POINTER(SolverOpts)]),
     "tp_filter_destroy": (_i, [_vp]),
     "tp_filter_stencil_width": (_i, [_vp]),
@@ -164,16 +152,6 @@ SYMBOLS = {
     "tp_pdefilter_solve": (_i, [_vp, _vp, _vp]),
     "tp_pdefilter_node_to_elem": (_i, [_vp, _vp, _vp]),
     "tp_pdefilter_apply": (_i, [_vp, _vp, _vp]),
-    "tp_pdefilter_level_count": (_i, [_vp]),
-    "tp_pdefilter_level_nodes": (_l, [_vp, _i]),
-    "tp_pdefilter_level_lambda": (_d, [_vp, _i]),
-    "tp_pdefilter_level_lambda_min": (_d, [_vp, _i]),
-    "tp_pdefilter_level_apply": (_i, [_vp, _i, _vp, _vp]),
-    "tp_pdefilter_level_diag": (_i, [_vp, _i, _vp]),
-    "tp_pdefilter_smooth": (_i, [_vp, _i, _vp, _vp, _i, _i]),
-    "tp_pdefilter_restrict": (_i, [_vp, _i, _vp, _vp]),
-    "tp_pdefilter_prolong_add": (_i, [_vp, _i, _vp, _vp]),
-    "tp_pdefilter_last_op_form": (_i, [_vp, C.POINTER(_i)]),
     "tp_mma_create": (_i, [C.POINTER(_vp), _vp, _l, _l, _i, _vp]),
     "tp_mma_destroy": (_i, [_vp]),
     "tp_mma_set_outer_movelimit": (_i, [_vp, _d, _d, _d, _vp, _vp, _vp]),
@@ -251,19 +229,27 @@ SYMBOLS = {
     "tp_conduction_response": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_d), _vp, _d, _d, _d, _d, C.POINTER(_d),
                                     C.POINTER(_d), C.POINTER(_d), _vp, _vp]),
     "tp_conduction_set_tolerances": (_i, [_vp, _d, _d, _d, _i]),
-    "tp_conduction_level_count": (_i, [_vp]),
-    "tp_conduction_level_nodes": (_l, [_vp, _i]),
-    "tp_conduction_level_lambda": (_d, [_vp, _i]),
-    "tp_conduction_level_lambda_min": (_d, [_vp, _i]),
-    "tp_conduction_level_apply": (_i, [_vp, _i, _vp, _vp]),
-    "tp_conduction_level_diag": (_i, [_vp, _i, _vp]),
-    "tp_conduction_smooth": (_i, [_vp, _i, _vp, _vp, _i, _i]),
-    "tp_conduction_level_residual": (_i, [_vp, _i, _vp, _vp, _vp]),
-    "tp_conduction_restrict": (_i, [_vp, _i, _vp, _vp]),
-    "tp_conduction_prolong_add": (_i, [_vp, _i, _vp, _vp]),
-    "tp_conduction_last_op_form": (_i, [_vp, C.POINTER(_i)]),
-    "tp_conduction_last_stats": (_i, [_vp, C.POINTER(_d), C.POINTER(_d), C.POINTER(_l)]),
 }
+
+# the hierarchy level by level: one surface (csrc/mg_levels.h) under three prefixes; the PDE filter has no residual, no stats
+_LEVEL_CALLS = {
+    "level_count": (_i, []),
+    "level_nodes": (_l, [_i]),
+    "level_lambda": (_d, [_i]),
+    "level_lambda_min": (_d, [_i]),
+    "level_apply": (_i, [_i, _vp, _vp]),
+    "level_diag": (_i, [_i, _vp]),
+    "smooth": (_i, [_i, _vp, _vp, _i, _i]),
+    "restrict": (_i, [_i, _vp, _vp]),
+    "prolong_add": (_i, [_i, _vp, _vp]),
+    "last_op_form": (_i, [C.POINTER(_i)]),
+    "level_residual": (_i, [_i, _vp, _vp, _vp]),
+    "last_stats": (_i, [C.POINTER(_d), C.POINTER(_d), C.POINTER(_l)]),
+}
+for _prefix, _without in (("tp_elasticity", ()), ("tp_conduction", ()), ("tp_pdefilter", ("level_residual", "last_stats"))):
+    for _suffix, (_res, _args) in _LEVEL_CALLS.items():
+        if _suffix not in _without:
+            SYMBOLS["%s_%s" % (_prefix, _suffix)] = (_res, [_vp] + _args)
 
 
 ABI_VERSION = 4   # TP_ABI_VERSION of include/topopt_amd.h
