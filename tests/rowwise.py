@@ -357,17 +357,76 @@ class PdeRef:
 # =====================================================================================================================
 XMIN = 1e-3
 GENERATORS = ("blocks", "checker", "one_solid", "one_void", "zlayer")
+# =====================================================================================================================
+# z-slabs: the cases on which the elasticity hierarchy's slab forms are to be held (tests/test_rowwise_oracle.py holds the float64
+# oracle to a quarter of every constant on them; the device side is not in the tree yet).  A row's arithmetic does not depend on
+# who owns it: the one-rank constants above hold row for row (level 1's correction adds its gathered products to the tile's sum
+# on one rank and on slabs alike, compact ghost rows included: the same count).  The fused dot products alone have a longer
+# chain: c_dot_slab.
+# =====================================================================================================================
+SLAB_GENERATORS = GENERATORS + ("seam_step", "seam_void")       # design(kind, ..., nranks=): the last two need the rank count
+# (mesh in elements, ranks): two element layers per rank, the thinnest the library accepts (the middle rank's interior pass is
+# empty) / odd ez_own, 510 nodes per plane pair / nx = 32, ny = 16 on the seams of both tile shapes, 8 planes per rank / two
+# ranks (the auto form only): both are end ranks, an even split
+SLAB_FINE = [((16, 8, 6), 3), ((33, 4, 9), 3), ((31, 15, 24), 3), ((31, 15, 12), 2)]
+# (mesh, ranks, levels): the one-rank coarse mesh in x and y, two layers per rank on level 2 / two layers per rank on level 3 /
+# ONE layer per rank on the coarsest level (check_solver_opts allows it: that level is solved on its replicated copy; the
+# slab's own stored stencil there feeds that copy and is held like every other level)
+SLAB_COARSE = [((36, 28, 24), 3, 3), ((24, 8, 48), 3, 4), ((16, 8, 12), 3, 3)]
+
+
+def slab_inputs(job, m, scattered, l, n, nc):
+    """(u, b, xc) of level l: seeded GLOBAL vectors of n and nc (next coarser level; 0: none) entries, the same on every rank
+    and in the parent"""
+    rng = np.random.default_rng(20000 + 5000 * (job == "coarse") + 100 * m + 10 * scattered + l)
+    return rng.standard_normal(n), rng.standard_normal(n), rng.standard_normal(nc)
+
+
+def slab_bc(orc, nx, ny, nz, h, scattered, seed):
+    """(N, R) on the GLOBAL mesh: the cantilever, or the scattered Dirichlet mask of tests/rowwise_worker.py: bc"""
+    if not scattered:
+        return orc.cantilever_bc(nx, ny, nz, h)
+    rng = np.random.default_rng(seed)
+    N = np.ones(3 * nx * ny * nz)
+    N[rng.random(N.size) < 2e-2] = 0.0
+    N[: 3 * nx] = 0.0
+    return N, rng.standard_normal(N.size) * 1e-3
+
+
+def slab_owned_planes(nz, nranks):
+    """node planes each rank owns: ez_own each, rank 0 also plane 0"""
+    own = (nz - 1) // nranks
+    return [own + (1 if r == 0 else 0) for r in range(nranks)]
+
+
+def c_dot_slab(kzs, nwgs):
+    """a fused dot product on slabs: rank r's partial goes through dot_chain(kzs[r], nwgs[r]) over its own workgroups, the
+    all-reduce adds nranks - 1 more additions: the power of two above the longest such chain.  Holds for any float64 summation of
+    that depth: no oracle figure, like c_dot"""
+    return _pow2(max(dot_chain(k, w) for k, w in zip(kzs, nwgs)) + len(nwgs) - 1)
+
+
 # node planes that carry block faces: the seams of the 15-node tiles (15, 30 -> 14..16, 30..32 with the tiles' overlap) and of
 # the 31 x 7 tiles (31; 7, 14), and one plane either side of them
 _FX = (13, 14, 15, 16, 17, 29, 30, 31, 32, 33)
 _FY = (5, 6, 7, 8, 9, 13, 14, 15, 16, 17)
 
 
-def design(kind, ex, ey, ez, kz=8):
+def design(kind, ex, ey, ez, kz=8, nranks=1):
     """-> float64 array of ex ey ez densities; kz: z-chunk length of the kernel under test (node planes per chunk), or a tuple
-    of the lengths of several forms (product and Chebyshev step may chunk differently): a solid layer at every boundary"""
+    of the lengths of several forms (product and Chebyshev step may chunk differently): a solid layer at every boundary;
+    nranks: the z-slabs of the two seam designs (SLAB_GENERATORS), ez / nranks element layers each"""
     solid = np.zeros((ez, ey, ex), dtype=bool)
-    if kind == "blocks":
+    if kind in ("seam_step", "seam_void"):
+        assert nranks >= 2 and ez % nranks == 0 and ez // nranks >= 2, (kind, ez, nranks)
+        own = ez // nranks
+        if kind == "seam_step":         # slab r solid for even r: solid below the first seam and void above it, the reverse at the next
+            solid[(np.arange(ez) // own) % 2 == 0] = True
+        else:                           # the element layer below and the one above every seam void, everything else solid
+            solid[:] = True
+            for r in range(1, nranks):
+                solid[r * own - 1:r * own + 1] = False
+    elif kind == "blocks":
         # block m: one with its LOW faces on the planes i = _FX[m], j = _FY[m], one with its HIGH faces there (they touch along
         # an edge only), w = 2..4 elements wide, in a band of two element layers of its own
         for m in range(len(_FX)):
